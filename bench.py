@@ -7,10 +7,14 @@ sensitive parameters, L=7, eps=1e-4, 16 independent chains per GPU (weak scaling
 GPUs), log-posterior + gradient on the HIP engine. One bench "step" = one HMC iteration of every
 local chain (momentum draw, L leapfrog steps, Metropolis accept), all device-resident.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
-Prints one JSON line on rank 0 (contract in the task statement / DESIGN.md §Measurement).
+A plain run sets up, warms up, times the K steps and prints one JSON line on rank 0 (the headline figure, its
+ms_per_step, the shader clock over the timed region). --dump-outputs DIR also writes what the last timed step left
+in the sampler (DIR/<name>.npy). --full adds everything else: the per-class roofline (HIP-event calibration before
+the timed region, the dominant class under events inside it), the sustained leg, ESS/s, the side legs and the CPU
+baselines.
 """
 import argparse
 import json
@@ -42,6 +46,13 @@ def parse():
     ap.add_argument("--chains-per-gpu", type=int, default=16)
     ap.add_argument("--L", type=int, default=7)
     ap.add_argument("--step-size", type=float, default=1e-4)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the sampler state the last timed step produced (theta, logp, "
+                         "grad of every chain, and the accept / log-prob traces of the timed steps) as DIR/<name>.npy "
+                         "(float32); the inputs and seeds depend on the arguments only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: roofline calibration and dominant-class "
+                         "events, sustained leg, ESS phase, side legs, CPU baselines (the options below apply to it)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--ess-steps", type=int, default=100,
                     help="HMC iterations of a separately timed phase after the timed region whose samples give "
@@ -442,6 +453,53 @@ def ess_phase(args, ev, runner, K, dev, chains, world):
                         "eps=1e-4 trajectories are short, so coordinate ESS is low"}
 
 
+def roofline_fields(eng, cal, dom_cls, fl, C, k_ms, k_n, clk):
+    """--full: the dominant class (chosen by the calibration `cal`) priced from its HIP events in the timed region."""
+    key, kname, what = KCLASS[dom_cls]
+    per_eval = cal[key]["launches_per_eval"]
+    flops_launch = C * fl[key] / max(per_eval, 1.0)
+    avg_s = (k_ms / max(k_n, 1)) / 1e3
+    achieved = flops_launch / avg_s / 1e12 if k_n else None
+    form_key = {"contract_a": "contract_bf16x6", "contract_b": "contract_bf16x6", "bwd": "bwd_bf16x6",
+                "fwd": "fwd_bf16x6", "gram": "contract_bf16x6"}[key]
+    bf = eng.get_option(form_key)
+    peak = mfma_peak(bf)
+    traffic, tsrc = load_traffic(kname, C)
+    return {
+        "roofline_frac_at_sclk": ((achieved / (peak * clk["mean_mhz"] / 2400.0))
+                                  if (achieved and clk["mean_mhz"] and clk["spread"] is not None
+                                      and clk["spread"] <= 0.10) else None),
+        "roofline_frac_at_sclk_basis": "the roofline fraction against the peak scaled to the measured clock; reported "
+                                       "only when the per-XCD spread is <= 10 %",
+        "roofline": {"kernel": f"{kname}: {what}", "selected_as": "largest share of the evaluation's GPU time "
+                     f"({cal[key]['share_of_eval']:.3f}, HIP-event calibration before the timed region)",
+                     "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
+                     "frac": (achieved / peak) if achieved else None, "traffic": traffic,
+                     "peak_basis": ("fp32-equivalent: bf16 dense MFMA peak 2516.6 / 6 bf16 products per fp32 product"
+                                    if bf else "fp32 MFMA dense peak"),
+                     "achieved_vs_fp32_mfma_peak": (achieved / FP32_PEAK_TFLOPS) if achieved else None,
+                     "traffic_unit": "HBM bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 passes; "
+                                     f"profiles/traffic.json: {tsrc})",
+                     "avg_launch_ms": avg_s * 1e3, "launches": k_n, "launches_per_eval": per_eval,
+                     "flops_per_launch": flops_launch},
+        "roofline_all": cal,
+    }
+
+
+def dump_outputs(out_dir, runner, first, rank):
+    """What the last timed step left in the sampler, as a caller of the runner reads it: every chain's state (theta,
+    its log-prob and gradient) and the accept / log-prob traces of the timed steps (from iteration `first` on). A few
+    MB at the bench shape; rank r > 0 writes under out_dir/rank<r>."""
+    d = out_dir if rank == 0 else os.path.join(out_dir, f"rank{rank}")
+    os.makedirs(d, exist_ok=True)
+    theta, logp, grad = runner.cur
+    res = runner.result()
+    arrays = {"theta": theta, "logp": logp, "grad": grad, "accepted": res.accepted[:, first:],
+              "logp_trace": res.logp_trace[:, first:]}
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -469,29 +527,33 @@ def main():
     chains = list(range(rank * C, (rank + 1) * C))
     theta0 = torch.tensor(prob.mu[prob.grad_ind], device=dev).repeat(C, 1)
     ev = EngineEvaluator(eng)
-    n_total = args.warmup + CAL_STEPS + args.steps
+    # the roofline's calibration iterations run only with --full
+    cal_steps = CAL_STEPS if args.full else 0
+    n_total = args.warmup + cal_steps + args.steps
     runner = HMCRunner(ev, theta0, n_total, args.L, args.step_size, burn=0,
                        rng=ChainRNG(C, eng.K, dev, seeds=[1000 + c for c in chains]))
     for _ in range(args.warmup):
         runner.step()
     torch.cuda.synchronize()
-    # calibration (untimed): every kernel class and the whole evaluation under HIP events for a few steps,
-    # to find the kernel class with the largest share of the evaluation -- the one the roofline prices
-    cal_steps = CAL_STEPS
-    eng.timing(-1, True)
-    for _ in range(cal_steps):
-        runner.step()
-    torch.cuda.synchronize()
-    cal = class_table(eng, spec, prob, C, cal_steps * args.L)
-    eng.timing(-1, False)
-    dom_cls = max(KCLASS, key=lambda k: cal.get(KCLASS[k][0], {}).get("share_of_eval", -1.0))
+    cal, dom_cls = None, None
+    if args.full:
+        # calibration (untimed): every kernel class and the whole evaluation under HIP events for a few steps,
+        # to find the kernel class with the largest share of the evaluation -- the one the roofline prices
+        eng.timing(-1, True)
+        for _ in range(cal_steps):
+            runner.step()
+        torch.cuda.synchronize()
+        cal = class_table(eng, spec, prob, C, cal_steps * args.L)
+        eng.timing(-1, False)
+        dom_cls = max(KCLASS, key=lambda k: cal.get(KCLASS[k][0], {}).get("share_of_eval", -1.0))
     ev.n_grad = 0
     eng.option("gram_evals", 0)                     # reset the plan's evaluation counters (both forms)
     clock = ShaderClock(dev)
-    # the dominant class under HIP events on every DOM_EVERY-th evaluation of the timed region (each event record
-    # leaves a few-us idle gap before the next launch: instrumentation, not workload)
-    eng.option("timing_every", DOM_EVERY)
-    eng.timing(dom_cls, True)
+    if args.full:
+        # the dominant class under HIP events on every DOM_EVERY-th evaluation of the timed region (each event record
+        # leaves a few-us idle gap before the next launch: instrumentation, not workload)
+        eng.option("timing_every", DOM_EVERY)
+        eng.timing(dom_cls, True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -504,9 +566,11 @@ def main():
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
-    k_ms, k_n = eng.timing_class(dom_cls)
-    eng.timing(-1, False)
-    eng.option("timing_every", 1)
+    k_ms, k_n = 0.0, 0
+    if args.full:
+        k_ms, k_n = eng.timing_class(dom_cls)
+        eng.timing(-1, False)
+        eng.option("timing_every", 1)
     grad_evals = ev.n_grad
     n_calls, n_gram = eng.get_option("grad_evals"), eng.get_option("gram_evals")
     clk = clock.summary()
@@ -524,12 +588,14 @@ def main():
         extra["allgather_bytes"] = pool.numel() * 4
     res = runner.result()
     acc_rate = float(res.accepted[:, args.warmup + cal_steps:].float().mean())
-    if T < 2.0:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, args.warmup + cal_steps, rank)
+    if args.full and T < 2.0:
         extra.update(sustained_leg(runner, eng, dev, C, args.L, world, ms_per_step=T / args.steps * 1e3))
-    if args.ess_steps > 0:
+    if args.full and args.ess_steps > 0:
         extra.update(ess_phase(args, ev, runner, eng.K, dev, chains, world))
     side = {}
-    if world == 1 and args.side_legs:
+    if args.full and world == 1 and args.side_legs:
         side["deeponet_1_chain"] = leg_deeponet_c1(prob, spec, dev, args.L, args.step_size)
         side["deeponet_good_fit_16_chains"] = leg_good_fit(spec, dev, args.L, args.step_size, C=C)
         side["config4_split_1_chain"] = leg_split_c1(spec, dev, args.L, args.step_size)
@@ -542,22 +608,12 @@ def main():
         return
     leapfrog = world * C * args.L * args.steps
     value = leapfrog / T
-    key, kname, what = KCLASS[dom_cls]
     fl = class_flops(eng, spec, prob)
-    per_eval = cal[key]["launches_per_eval"]
-    flops_launch = C * fl[key] / max(per_eval, 1.0)
-    avg_s = (k_ms / max(k_n, 1)) / 1e3
-    achieved = flops_launch / avg_s / 1e12 if k_n else None
     evals_per_s = world * grad_evals / T
     gram_frac = n_gram / max(n_calls, 1)
     fl_res = spec.flops_per_grad_eval(prob.N, prob.P)
     fl_gram = fl_res - fl["contract_a"] - fl["contract_b"] + fl["gram"]
     flops_performed = (1.0 - gram_frac) * fl_res + gram_frac * fl_gram
-    form_key = {"contract_a": "contract_bf16x6", "contract_b": "contract_bf16x6", "bwd": "bwd_bf16x6",
-                "fwd": "fwd_bf16x6", "gram": "contract_bf16x6"}[key]
-    bf = eng.get_option(form_key)
-    peak = mfma_peak(bf)
-    traffic, tsrc = load_traffic(kname, C)
     line = {
         "metric": METRIC,
         "value": value,
@@ -597,25 +653,11 @@ def main():
                       "workgroups paired by XCD / CU; MI355X_MICROARCH.md DVFS item 6); per XCD the median over its "
                       "CUs; readings above the 2,400-MHz maximum rejected and listed; spread = (max - min) / mean "
                       "over the XCD medians",
-        "roofline_frac_at_sclk": ((achieved / (peak * clk["mean_mhz"] / 2400.0))
-                                  if (achieved and clk["mean_mhz"] and clk["spread"] is not None
-                                      and clk["spread"] <= 0.10) else None),
-        "roofline_frac_at_sclk_basis": "the roofline fraction against the peak scaled to the measured clock; reported "
-                                       "only when the per-XCD spread is <= 10 %",
         "accept_rate": acc_rate,
-        "roofline": {"kernel": f"{kname}: {what}", "selected_as": "largest share of the evaluation's GPU time "
-                     f"({cal[key]['share_of_eval']:.3f}, HIP-event calibration before the timed region)",
-                     "bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
-                     "frac": (achieved / peak) if achieved else None, "traffic": traffic,
-                     "peak_basis": ("fp32-equivalent: bf16 dense MFMA peak 2516.6 / 6 bf16 products per fp32 product"
-                                    if bf else "fp32 MFMA dense peak"),
-                     "achieved_vs_fp32_mfma_peak": (achieved / FP32_PEAK_TFLOPS) if achieved else None,
-                     "traffic_unit": "HBM bytes/launch (PMC FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 passes; "
-                                     f"profiles/traffic.json: {tsrc})",
-                     "avg_launch_ms": avg_s * 1e3, "launches": k_n, "launches_per_eval": per_eval,
-                     "flops_per_launch": flops_launch},
-        "roofline_all": cal,
+        "full": args.full,
     }
+    if args.full:
+        line.update(roofline_fields(eng, cal, dom_cls, fl, C, k_ms, k_n, clk))
     line.update(extra)
     if side:
         line["side_legs"] = side
@@ -625,7 +667,7 @@ def main():
         side["bnn_config2_1_chain"]["speedup_vs_cpu"] = side["bnn_config2_1_chain"]["leapfrog_steps_per_s"] / bc["value"]
         side["bnn_config3_8_chains"]["speedup_per_chain_vs_cpu"] = \
             side["bnn_config3_8_chains"]["leapfrog_steps_per_s"] / 8 / bc["value"]
-    if world == 1 and args.cpu_seconds > 0:
+    if args.full and world == 1 and args.cpu_seconds > 0:
         cb = cpu_baseline(prob, args.L, args.step_size, args.cpu_seconds)
         line["cpu_baseline"] = cb
         line["speedup_vs_cpu"] = value / cb["value"]

@@ -7,8 +7,8 @@ TAG=${1:-r02}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$ROOT/gpurun_out
 mkdir -p $O
-B="python3 $ROOT/bench.py --steps 5 --warmup 1 --cpu-seconds 0 --no-side-legs"
-timeout -k 10 600 python3 $ROOT/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err && \
+B="python3 $ROOT/bench.py --full --steps 5 --warmup 1 --cpu-seconds 0 --no-side-legs"
+timeout -k 10 600 python3 $ROOT/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err && \
 cd /tmp && export TMPDIR=/tmp && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o s -- $B \
     > $O/${TAG}_stats.log 2>&1 && \

@@ -16,7 +16,7 @@ rc=$?; echo "tests rc=$rc"; tail -3 $O/${TAG}_tests.txt
 if [ "${CAL:-0}" = 1 ]; then [ $rc -le 1 ] || exit $rc; else [ $rc -eq 0 ] || exit $rc; fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.txt 2>&1 || exit 1
 [ "${BENCH:-1}" = 1 ] || exit 0
-timeout -k 10 600 python -u bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?; echo "bench rc=$rc"
+timeout -k 10 600 python -u bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?; echo "bench rc=$rc"
 [ $rc -eq 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o s -- \

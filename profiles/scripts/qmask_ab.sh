@@ -14,7 +14,7 @@ rc=$?; tail -3 gpurun_out/${TAG}_tests.txt; [ $rc -eq 0 ] || exit $rc
 for rep in 1 2; do
   for L in base qm; do
     echo "== $L rep $rep" >> $O
-    VIHMC_LIB=$ROOT/_ab/$L.so timeout -k 10 200 python -u bench.py --cpu-seconds 0 --no-side-legs --ess-steps 0 >> $O 2>/dev/null || exit 1
+    VIHMC_LIB=$ROOT/_ab/$L.so timeout -k 10 200 python -u bench.py --full --cpu-seconds 0 --no-side-legs --ess-steps 0 >> $O 2>/dev/null || exit 1
     VIHMC_LIB=$ROOT/_ab/$L.so timeout -k 10 150 python -u profiles/scripts/probes/probe_legs.py --reps 1 >> $O 2>/dev/null || exit 1
   done
 done

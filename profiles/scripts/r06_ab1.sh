@@ -10,7 +10,7 @@ for rep in 1 2; do
     timeout -k 10 120 python -u $P --chains 16 --iters 20 --grad $a --tag "$v" >> $O/r06_ab1.txt 2>&1 || exit 1
   done
 done
-timeout -k 10 600 python -u bench.py --steps 20 --cpu-seconds 0 > $O/r06_bench20.json 2> $O/r06_bench20.err || exit 1
+timeout -k 10 600 python -u bench.py --full --steps 20 --cpu-seconds 0 > $O/r06_bench20.json 2> $O/r06_bench20.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r06_stats -o s -- \
     python3 ${GRAFT_REPO_ROOT}/bench.py --steps 40 --warmup 3 --cpu-seconds 0 --no-side-legs --ess-steps 0 \

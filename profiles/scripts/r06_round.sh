@@ -25,7 +25,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.txt 2>&1 || exit 1
 fi
 [ "${BENCH:-1}" = 1 ] || exit 0
-timeout -k 10 600 python -u bench.py --steps 20 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?; echo "bench rc=$rc"
+timeout -k 10 600 python -u bench.py --full --steps 20 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; rc=$?; echo "bench rc=$rc"
 [ $rc -eq 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -o s -- \
