@@ -151,6 +151,18 @@ int vihmc_kinetic(const float* p, const float* inv_mass, int C, int K, float* ke
  * Replaces log_prob_func(..., predict=True) -> (logp, output) (main_VI_HMC_burgers.py:175-176). */
 int vihmc_forward(vihmc_plan* p, const float* theta, int C, float* logp, float* out, void* stream);
 
+/* DeepONet plans: posterior-predictive moments of C samples without their [C, N, P] output. For c = 0 .. C-1 in
+ * order, sum1[n][p] += S_c[n][p] and sum2[n][p] += S_c[n][p]^2 in fp64, S_c bit for bit the `out` of vihmc_forward;
+ * sum1 / sum2 are caller-owned DEVICE [N][P] doubles, read only when accumulate != 0 (0: they start from zero). The
+ * additions run in chain order into the running value, so the state does not depend on how a sample list is cut
+ * into calls. sse_rows (DEVICE [C][N] doubles, or NULL) receives sum_p (S_c - y)^2 per function, excluded (NaN)
+ * targets of a masked plan counting 0; logp [C] is vihmc_forward's. Uses the trunk rows / data the plan holds
+ * (vihmc_plan_set_trunk_rows, vihmc_plan_set_data). BNN plans: an error. Replaces the prediction list and its
+ * np.mean / np.std(pred_list, axis=0) (Operator_network/VI_HMC/post_process_burgers.py:85-95), the per-sample MSE
+ * of predict_model (main_VI_HMC_burgers.py:183-241) and print_error's relative L2 (post_process_burgers.py:105-146). */
+int vihmc_predict_moments(vihmc_plan* p, const float* theta, int C, float* logp, double* sum1, double* sum2,
+                          int accumulate, double* sse_rows, void* stream);
+
 /* BNN plans: one whole leapfrog trajectory of every chain in ONE launch (hamiltorch leapfrog,
  * Sampler.HMC with the implicit integrator): from theta_in [C, K], the fresh momentum
  * p_in [C, K] and the gradient g_in [C, K] at theta_in, L steps of size eps[c] (device [C]; inv_mass [K]

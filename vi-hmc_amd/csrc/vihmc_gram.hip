@@ -57,8 +57,8 @@ static_assert(GRAM_P3_BLOCK % 1024 == 0, "whole DMA pieces");
 constexpr int GR_CW = 8;                                  // compute waves (32 rows each)
 constexpr int GR_THREADS = 64 * (GR_CW + 1);              // + one DMA wave
 // centred form (GramArgs::center): k_gram_a's Gram units stream the output image AND the centre's image (ring slots
-// of two blocks); k_gram_b runs 8 extension blocks (-Gb, then -Hb) and its dZb units stage Gt (fp64), Ht (fp32),
-// dB^T and B0^T
+// of two blocks); k_gram_b runs 8 extension blocks (-Gb, then -Hb) and its dZb units stage Gt and Ht (both fp32:
+// dzb_unit_c's terms are of the residual's size; only the uncentred dzb_unit keeps Gt in fp64), dB^T and B0^T
 constexpr int GR_LDS_C = GR_NBUF * 2 * GR_BLK;            // 126 KB
 constexpr int GRB_LDS_TC = GR_LDS;                       // 64.5 KB: no 4th planes
 constexpr int GRB_DZBC = 2 * 101 * 112 * 4 + 2 * 101 * 32 * 4;               // 116,352 B

@@ -207,6 +207,30 @@ struct ContractProb {
 };
 
 // ---------------------------------------------------------------------------------------------
+// Posterior-predictive moments (vihmc_moments.hip): for the C chains of a call, in chain order,
+//   sum1[n][p] += S_c[n][p], sum2[n][p] += S_c[n][p]^2 (fp64 state, caller-owned [N][P]), S_c = Zb_c Zt_c^T + b0_c
+// bit for bit the forward's, and per (chain, n) the fp64 sum over p of (S - y)^2. A workgroup owns a
+// MOMENTS_TILE_N x MOMENTS_TILE_P tile of the state and loops over the chains; S is never stored.
+// ---------------------------------------------------------------------------------------------
+constexpr int MOMENTS_TILE_N = 64;
+constexpr int MOMENTS_TILE_P = 128;
+struct MomentsProb {
+    const float* Zb; int64_t zb_cs;       // branch outputs [N][ldz] per chain
+    const float* Zt; int64_t zt_cs;       // trunk outputs [P][ldz] per chain
+    int32_t ldz;
+    const float* Y; int32_t ldy;          // targets [N][ldy], shared by the chains
+    int32_t masked;                       // a NaN target marks an excluded (row, point) pair (residual 0)
+    const float* b0; int64_t b0_cs;
+    double* sum1; double* sum2;           // [N][P]
+    int32_t accumulate;                   // 0: the state starts at zero (it is not read)
+    double* part;                         // [C][p_tiles][N] sums of r^2 over one p tile
+    double* sse_rows;                     // [C][N] or null
+    double* stats; int64_t stats_cs;      // per chain n_tiles pairs (sum r^2, 0): StatsJob's layout, a "wave" per n tile
+    int32_t N, P, W, C, n_tiles, p_tiles;
+};
+hipError_t launch_predict_moments(const MomentsProb& p, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------
 // Gradient-only contraction in Gram form (vihmc_gram.hip): dZ_b and dZ_t from y Zt^, y^T Zb^ and the two
 // 101 x 101 Gram matrices of the augmented outputs Zb^ = [Z_b | 1], Zt^ = [Z_t | b0]; no residual, no G^T.
 // ---------------------------------------------------------------------------------------------

@@ -249,6 +249,8 @@ struct vihmc_plan {
     int debug_dz = 0;                 // plan option (diagnostics): keep each evaluation's dZ_b / dZ_t
     float* dzb_snap = nullptr;
     float* dzt_snap = nullptr;
+    double* msse_part = nullptr;      // vihmc_predict_moments: [maxC][p tiles][N] sums of r^2 (allocated by its first call)
+    double* msse_stats = nullptr;     // ... [maxC][n tiles] (sum r^2, 0) pairs
     unsigned char* cimgB = nullptr;   // B0 pre-split image (qsplitA_cs bytes)
     unsigned char* cimgT = nullptr;   // T0 pre-split image (qsplitB_cs bytes)
     float* cB0 = nullptr;             // B0 fp32 rows [N][ldz]
@@ -1633,6 +1635,60 @@ int deeponet_eval_body(vihmc_plan* p, const float* theta, int C, float* logp, fl
     return 0;
 }
 
+// vihmc_predict_moments: the forward evaluation's launches with k_predict_moments in place of the predict contraction
+// (no [C, N, P] output anywhere); the likelihood from its per-chain sum r^2 through the same statistics + prior launches
+int deeponet_predict_moments(vihmc_plan* p, const float* theta, int C, float* logp, double* sum1, double* sum2,
+                             int accumulate, double* sse_rows, hipStream_t s) {
+    if (C < 1 || C > p->maxC) return fail("C must be in [1, max_chains]");
+    const int p_tiles = cdiv(p->P, MOMENTS_TILE_P);
+    const int n_tiles = cdiv(p->N, MOMENTS_TILE_N);
+    if (!p->msse_part) {
+        if (int rc = p->alloc(&p->msse_part, (int64_t)p->maxC * p_tiles * p->N)) return rc;
+        if (int rc = p->alloc(&p->msse_stats, (int64_t)p->maxC * n_tiles * 2)) return rc;
+    }
+    ++p->n_evals;
+    hipEvent_t stop = nullptr;
+    if (int rc = p->timing_begin(VIHMC_T_EVAL, s, &stop)) return rc;
+    const ScatterImg si = scatter_img(p);
+    HIPCHK(launch_scatter(p->packed, p->dp, C, theta, p->K, p->smap_w, p->smap_wt, s, p->img_by_scatter ? &si : nullptr));
+    p->img_by_fwd = false;
+    p->timg_live = p->img_by_scatter && p->wtimg;
+    if (int rc = deeponet_forward_layers(p, C, s, false, false)) return rc;
+    Net& b = p->nets[0];
+    Net& t = p->nets[1];
+    MomentsProb m{};
+    m.Zb = b.act + b.h_off.back();
+    m.zb_cs = b.act_cs;
+    m.Zt = t.act + t.h_off.back();
+    m.zt_cs = t.act_cs;
+    m.ldz = p->ldz;
+    m.Y = p->y;
+    m.ldy = p->P;
+    m.masked = p->y_masked;
+    m.b0 = p->packed;
+    m.b0_cs = p->dp;
+    m.sum1 = sum1;
+    m.sum2 = sum2;
+    m.accumulate = accumulate ? 1 : 0;
+    m.part = p->msse_part;
+    m.sse_rows = sse_rows;
+    m.stats = p->msse_stats;
+    m.stats_cs = 2 * (int64_t)n_tiles;
+    m.N = p->N;
+    m.P = p->P;
+    m.W = p->W;
+    m.C = C;
+    m.n_tiles = n_tiles;
+    m.p_tiles = p_tiles;
+    HIPCHK(launch_predict_moments(m, s));
+    StatsJob stats_job{m.stats, m.stats_cs, n_tiles, p->lik_buf, p->gp, p->dp, lik_count(p), p->lik.loss, p->lik.tau_out};
+    HIPCHK(launch_contract_stats(stats_job, C, s));
+    HIPCHK(launch_gather_prior(p->gp, p->dp, p->smap_w, theta, p->K, p->prior_mu, p->prior_iv, p->prior_const,
+                               p->lik.prior_scale, p->lik_buf, C, logp, nullptr, p->lp_part, p->fin_cnt, s, nullptr));
+    if (stop) HIPCHK(hipEventRecord(stop, s));
+    return 0;
+}
+
 int mlp_eval(vihmc_plan* p, const float* theta, int C, float* logp, float* grad, float* out, hipStream_t s);
 
 // opt-in (VIHMC_GRAPH=1): measured 0.5-1 % slower than direct launches at C = 1, 4, 16 (the host enqueues an
@@ -2011,6 +2067,16 @@ int vihmc_forward(vihmc_plan* p, const float* theta, int C, float* logp, float* 
         hipStream_t s = static_cast<hipStream_t>(stream);
         return p->kind == 0 ? deeponet_eval(p, theta, C, logp, nullptr, out, s)
                             : mlp_eval(p, theta, C, logp, nullptr, out, s);
+    });
+}
+
+int vihmc_predict_moments(vihmc_plan* p, const float* theta, int C, float* logp, double* sum1, double* sum2,
+                          int accumulate, double* sse_rows, void* stream) {
+    return guarded([&]() -> int {
+        if (!p || !theta || !logp || !sum1 || !sum2) return fail("null argument");
+        if (p->kind != 0)
+            return fail("vihmc_predict_moments: DeepONet plans only (a BNN's [N, out_dim] outputs are reduced by the caller)");
+        return deeponet_predict_moments(p, theta, C, logp, sum1, sum2, accumulate, sse_rows, static_cast<hipStream_t>(stream));
     });
 }
 

@@ -54,6 +54,8 @@ SIGNATURES = {
     "vihmc_logp_grad": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vihmc_grad": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "vihmc_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vihmc_predict_moments": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_void_p]),
     "vihmc_hmc_accept": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 16 + [c_void_p, c_int64, c_void_p,
                                                                                    c_void_p, c_int64, c_void_p,
                                                                                    c_int64, c_void_p, c_void_p,

@@ -443,6 +443,32 @@ class DeepONetEngine(_Engine):
                                                    _lib.fptr(pm), _lib.fptr(ps), self.device.index)
         self._created(rc, "vihmc_deeponet_plan_create")
 
+    def predict_moments(self, theta: torch.Tensor, sum1: torch.Tensor, sum2: torch.Tensor, accumulate: bool = True,
+                        sse_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """vihmc_predict_moments: theta [C, K] -> logp [C], with the C predictions folded in chain order into the
+        fp64 [N, P] states ``sum1 += S_c`` and ``sum2 += S_c**2`` in place (``accumulate=False``: the states start
+        from zero) and, when given, ``sse_rows`` [C, N] fp64 = sum_p (S_c - y)^2. The [C, N, P] output of ``forward``
+        is never formed; every S_c is bit for bit ``forward``'s."""
+        th = self._theta(theta)
+        C = th.shape[0]
+        for name, a in (("sum1", sum1), ("sum2", sum2)):
+            if (not torch.is_tensor(a) or a.dtype != torch.float64 or a.device != self.device or not a.is_contiguous()
+                    or tuple(a.shape) != (self.N, self.P)):
+                raise ValueError(f"{name} must be a contiguous float64 [{self.N}, {self.P}] tensor on the plan's device "
+                                 "(updated in place)")
+        if sum1.data_ptr() == sum2.data_ptr():
+            raise ValueError("sum1 and sum2 must be different tensors")
+        if sse_rows is not None and (sse_rows.dtype != torch.float64 or sse_rows.device != self.device
+                                     or not sse_rows.is_contiguous() or tuple(sse_rows.shape) != (C, self.N)):
+            raise ValueError(f"sse_rows must be a contiguous float64 [{C}, {self.N}] tensor on the plan's device")
+        logp = torch.empty(C, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            rc = self.L.vihmc_predict_moments(self._plan, th.data_ptr(), C, logp.data_ptr(), sum1.data_ptr(),
+                                              sum2.data_ptr(), int(bool(accumulate)),
+                                              None if sse_rows is None else sse_rows.data_ptr(), self._stream())
+        _lib.check(rc, "vihmc_predict_moments")
+        return logp
+
 
 class MLPEngine(_Engine):
     """BNN regression log-posterior (Functional_Net + NLL/regression likelihood + Normal prior)."""

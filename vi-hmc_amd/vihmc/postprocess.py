@@ -7,6 +7,12 @@ Mirrors the reference's post-processing with the same file formats:
   main_VI_HMC_burgers.py:183-241,304-349), batched ``engine.max_chains`` samples per launch, returning the
   per-sample MSE and log-probability lists the reference prints, the fp64 posterior-predictive mean, and
   the per-sample per-function relative L2 errors of ``print_error`` (post_process_burgers.py:105-146);
+* ``predictive_moments`` -- the same contract plus the fp64 sum of squared predictions, from which ``Predictive.std``
+  / ``var`` / ``band`` give ``np.std(pred_list, axis=0)`` and the mean +- 3 sigma lines (post_process_burgers.py:85-95)
+  and ``prediction_std_{test_ind}.npy`` (:241,252); on a DeepONetEngine everything comes out of
+  ``vihmc_predict_moments`` and no [C, N, P] tensor exists;
+* ``error_uncertainty`` -- the per-time-slice mean absolute error, mean sigma and their correlation that
+  ``plot_correlation`` builds (:165-197);
 * ``post_burn_per_chain`` -- each chain's own stored samples after burn (chains that hit a LogProbError
   store fewer samples; nothing requires equal counts).
 
@@ -57,9 +63,30 @@ class Predictive:
     mse: List[float] = field(default_factory=list)         # per-sample mean squared error (reference order)
     log_prob: List[float] = field(default_factory=list)    # per-sample log-probability on the data
     rel_l2: List[np.ndarray] = field(default_factory=list)  # per-sample [N] relative L2 errors
+    pred_sqsum: torch.Tensor = None                        # fp64 [N, P] sum of squared predictions (predictive_moments)
 
     def mean(self) -> torch.Tensor:
         return self.pred_sum / max(self.n, 1)
+
+    def var(self, ddof: int = 0) -> torch.Tensor:
+        """Per-point variance of the predictions over the samples, fp64: max(sqsum / n - (sum / n)^2, 0) n / (n - ddof)."""
+        if self.pred_sqsum is None:
+            raise ValueError("this Predictive holds no sum of squares (made by predictive(); use predictive_moments())")
+        if self.n - ddof <= 0:
+            raise ValueError(f"variance with ddof={ddof} needs more than {ddof} samples (n={self.n})")
+        m = self.pred_sum.double() / self.n
+        v = torch.clamp(self.pred_sqsum.double() / self.n - m * m, min=0.0)
+        # clamp passes NaN through: a non-finite prediction gives a NaN variance, as np.std over such a list does
+        return v * (self.n / (self.n - ddof))
+
+    def std(self, ddof: int = 0) -> torch.Tensor:
+        """np.std(pred_list, axis=0) at ddof = 0 (post_process_burgers.py:86,252), torch.std(dim=0) at ddof = 1 (:179)."""
+        return torch.sqrt(self.var(ddof))
+
+    def band(self, k: float = 3.0):
+        """(mean - k sigma, mean + k sigma) at ddof = 0: the dashed lines of post_process_burgers.py:92-95."""
+        m, sd = self.mean(), self.std(0)
+        return m - k * sd, m + k * sd
 
 
 def predictive(engine, sample_sets: Sequence[torch.Tensor], y: torch.Tensor, with_rel_l2: bool = False) -> Predictive:
@@ -83,6 +110,72 @@ def predictive(engine, sample_sets: Sequence[torch.Tensor], y: torch.Tensor, wit
     return res
 
 
+def predictive_moments(engine, sample_sets: Sequence[torch.Tensor], y: torch.Tensor,
+                       with_rel_l2: bool = False) -> Predictive:
+    """``predictive`` with the sum of squared predictions as well (``Predictive.pred_sqsum``, so ``std`` / ``var`` /
+    ``band`` work). On a DeepONetEngine every batch is one ``engine.predict_moments`` call: the running fp64 sums stay on
+    the device, the per-sample MSE is sum_n sse_rows / (N P) and the relative L2 sqrt(sse_rows) / ||y_n|| with the
+    norms of y computed once; the engine's own targets must be ``y`` (as for ``predictive``'s log-probabilities). On an
+    MLPEngine the [C, N, out_dim] outputs of ``engine.forward`` are summed in torch fp64."""
+    dev = engine.device
+    yd = y.to(dev).reshape(engine.out_shape)
+    res = Predictive(pred_sum=torch.zeros(engine.out_shape, dtype=torch.float64, device=dev),
+                     pred_sqsum=torch.zeros(engine.out_shape, dtype=torch.float64, device=dev))
+    B = engine.max_chains
+    native = getattr(engine, "kind", None) == "deeponet"
+    with torch.no_grad():
+        if native:
+            count = float(yd.numel())
+            ynorm = torch.linalg.vector_norm(yd.double(), dim=-1) if with_rel_l2 else None
+            sse = torch.empty(B, engine.out_shape[0], dtype=torch.float64, device=dev)
+        for s in sample_sets:
+            s = s.to(dev, torch.float32)
+            for i in range(0, s.shape[0], B):
+                th = s[i:i + B]
+                C = th.shape[0]
+                if native:
+                    rows = sse[:C]
+                    lp = engine.predict_moments(th, res.pred_sum, res.pred_sqsum, accumulate=True, sse_rows=rows)
+                    res.mse += (rows.sum(1) / count).tolist()
+                    if with_rel_l2:
+                        res.rel_l2 += list((torch.sqrt(rows) / ynorm).cpu().numpy())
+                else:
+                    lp, out = engine.forward(th)
+                    o64 = out.double()
+                    for c in range(C):          # chain order into the running value, as the native path
+                        res.pred_sum += o64[c]
+                        res.pred_sqsum += o64[c] * o64[c]
+                    res.mse += ((out - yd) ** 2).mean(dim=tuple(range(1, out.dim()))).tolist()
+                    if with_rel_l2:
+                        res.rel_l2 += list(l2_relative_error_t(yd.double(), o64).cpu().numpy())
+                res.n += C
+                res.log_prob += lp.tolist()
+    return res
+
+
+def error_uncertainty(mean, std, y, nx: int, reference_mean: bool = False):
+    """The three lists ``plot_correlation`` builds (post_process_burgers.py:165-197), one entry per time slice of ``nx``
+    consecutive points: the mean absolute error |mean - y|, the mean standard deviation, and the Pearson correlation
+    of the two over the slice's [N, nx] entries. ``mean`` / ``std`` / ``y`` are [N, P] (P a multiple of nx); pass
+    ``Predictive.std(1)`` for the reference's ``torch.std`` (unbiased). ``reference_mean=True`` reproduces the
+    reference's ``torch.mean(pred_tensor)`` (:178), ONE scalar -- the mean over every sample, function and point of the
+    slice -- in place of the per-point posterior mean."""
+    m = np.asarray(torch.as_tensor(mean).detach().cpu(), dtype=np.float64)
+    sd = np.asarray(torch.as_tensor(std).detach().cpu(), dtype=np.float64)
+    yy = np.asarray(torch.as_tensor(y).detach().cpu(), dtype=np.float64).reshape(m.shape)
+    if m.ndim != 2 or sd.shape != m.shape or nx < 1 or m.shape[1] % nx:
+        raise ValueError("error_uncertainty needs mean / std / y of one shape [N, P] with P a multiple of nx")
+    errs, stds, corrs = [], [], []
+    for t in range(m.shape[1] // nx):
+        sl = slice(t * nx, (t + 1) * nx)
+        mt = m[:, sl].mean() if reference_mean else m[:, sl]
+        e = np.abs(mt - yy[:, sl])
+        errs.append(float(e.mean()))
+        stds.append(float(sd[:, sl].mean()))
+        corrs.append(float(np.corrcoef(e.ravel(), sd[:, sl].ravel())[0][1]))
+    return errs, stds, corrs
+
+
 def pool_ranks(p: Predictive) -> Predictive:
     """Job-wide predictive of a chain-sharded run: the prediction sums and counts all-reduced, the per-sample
     MSE / log-probability lists all-gathered in rank order (a few floats per sample), so every summary line
@@ -92,6 +185,8 @@ def pool_ranks(p: Predictive) -> Predictive:
         return p
     n = torch.tensor([float(p.n)], dtype=torch.float64, device=p.pred_sum.device)
     dist.all_reduce(p.pred_sum)
+    if p.pred_sqsum is not None:
+        dist.all_reduce(p.pred_sqsum)
     dist.all_reduce(n)
     p.n = int(n.item())
     lists = [None] * dist.get_world_size()
