@@ -296,9 +296,9 @@ int vihmc_clock_stamp(uint64_t* out, void* stream);
 
 void        vihmc_plan_destroy(vihmc_plan* p);
 const char* vihmc_last_error(void);
-/* "vihmc <ver> gfx950 diag=<n>": the VIHMC_DIAG value (csrc/vihmc_diag.h: timing-only ablations and phase stamps) the
- * library was built with (0 in a product build). Plan creation fails in a build with VIHMC_DIAG != 0 unless
- * VIHMC_ALLOW_DIAG=1 (A/B timing of variant builds only: results are wrong by design). */
+/* "vihmc <ver> gfx950 diag=<n>": the VIHMC_DIAG value (csrc/vihmc_diag.h: in-kernel phase stamps) the library was
+ * built with (0 in a product build). Plan creation fails in a build with VIHMC_DIAG != 0 unless VIHMC_ALLOW_DIAG=1
+ * (the stamp readers only: an instrumented build, whose stamps perturb timing). */
 const char* vihmc_version(void);
 
 #ifdef __cplusplus

@@ -290,10 +290,7 @@ __global__ __launch_bounds__(CH_THREADS, 1) void k_bwd_chain(BwdChainArgs A) {
 #pragma unroll
                             for (int p = 0; p < 3; ++p) db[p] = *reinterpret_cast<const bf16x8*>(drow + p * CH_PLANE + 64 * kb);
 #pragma unroll
-                            for (int u = 0; u < NU; ++u) {
-                                if (CH_ABL == 2) asm volatile("" :: "v"(wf[u][kb][0]), "v"(db[0]), "v"(db[1]), "v"(db[2]));
-                                else ac[u] = six(wf[u][kb], db, ac[u]);
-                            }
+                            for (int u = 0; u < NU; ++u) ac[u] = six(wf[u][kb], db, ac[u]);
                         }
                         // epilogue: act'(h_{j-1}), staged with h_{j-1} one layer ago (or in the prologue)
                         (void)act;
@@ -386,10 +383,6 @@ __global__ __launch_bounds__(CH_THREADS, 1) void k_bwd_chain(BwdChainArgs A) {
                     if (t + 1 < nt) {
 #pragma unroll
                         for (int p = 0; p < 3; ++p) hb[(t + 1) & 1][p] = tr_frag(hbuf + p * CH_PLANE, tro, 16 * (t + 1));
-                    }
-                    if (CH_ABL == 1) {
-                        asm volatile("" :: "v"(da[0][0]), "v"(da[1][0]), "v"(hb[t & 1][0]), "v"(hb[t & 1][1]), "v"(hb[t & 1][2]));
-                        continue;
                     }
                     acc[0][t] = six(da[0], hb[t & 1], acc[0][t]);
                     if (t >= cb0 && t < cb1) acc[1][t] = six(da[1], hb[t & 1], acc[1][t]);

@@ -39,8 +39,8 @@ __device__ __forceinline__ float tanh_f(float x) { return tanh_acc(x); }
 
 template <int ACT>
 __device__ __forceinline__ float act_t(float z) {
-    if constexpr (ACT == ACT_TANH) return (FWD_ABL & 2) ? z : tanh_f(z);
-    else if constexpr (ACT == ACT_TANH_CR) return (FWD_ABL & 2) ? z : tanh_cr(z);   // each net's last hidden layer
+    if constexpr (ACT == ACT_TANH) return tanh_f(z);
+    else if constexpr (ACT == ACT_TANH_CR) return tanh_cr(z);   // each net's last hidden layer
     else if constexpr (ACT == ACT_RELU) return fmaxf(z, 0.f);
     else return z;
 }
@@ -214,12 +214,10 @@ __global__ __launch_bounds__(NW * 64, 1) void k_fwd_fused(FusedArgs args) {
 //   holds slots 8g..8g+7 = h[m][16 t0 + 4g + 0..3] and h[m][16 t1 + 4g + 0..3] -- exactly registers
 //   0..3 of accumulators t0 and t1 of the previous layer, so activations need no lane movement. The
 //   weights are stored in LDS in that permuted order (one b128 per plane per fragment). The k tail
-//   (columns 96..99) is one exact 16x16x4 f32 MFMA per tile (FWD_TAILF32, below; the FWD_TAILF32 = 0 form
-//   runs six 16x16x16 bf16 MFMAs, whose k layout 4g + j is the accumulator's).
+//   (columns 96..99) is one exact 16x16x4 f32 MFMA per tile (the f32 k tail, below).
 // =============================================================================================
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BROW = 112;                         // bf16 per plane row (3 k-blocks x 32 + tile 6 x 16)
 constexpr int BPLANE = FW * BROW;                 // bf16 per plane
@@ -234,48 +232,6 @@ __device__ __forceinline__ void split3(float x, __bf16& a, __bf16& b, __bf16& c)
 
 __device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(bf16x4 a, bf16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c,
-                                                      0, 0, 0);
-}
-
-// one 16-row output tile t: acc += W[16t + lr][:] . h (six bf16 products per k-block)
-__device__ __forceinline__ f32x4 bf_tile(const __bf16* wb, int t, int lr, int lg, const bf16x8 (&hp)[3][3],
-                                         const bf16x4 (&h6)[3]) {
-    const int n = min(16 * t + lr, FW - 1);
-    const __bf16* row0 = wb + n * BROW;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 3; ++kb) {
-        const int o = kb * 32 + lg * 8;
-        const bf16x8 w0 = *reinterpret_cast<const bf16x8*>(row0 + o);
-        const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(row0 + BPLANE + o);
-        const bf16x8 w2 = *reinterpret_cast<const bf16x8*>(row0 + 2 * BPLANE + o);
-        acc = mfma32(w2, hp[0][kb], acc);
-        acc = mfma32(w1, hp[1][kb], acc);
-        acc = mfma32(w0, hp[2][kb], acc);
-        acc = mfma32(w1, hp[0][kb], acc);
-        acc = mfma32(w0, hp[1][kb], acc);
-        acc = mfma32(w0, hp[0][kb], acc);
-    }
-    // the K = 16 tail accumulates into its own registers: no accumulator chain crosses the two MFMA shapes.
-    // (Chaining a 16x16x32 result straight into a 16x16x16 MFMA's C operand gave wrong tiles with the
-    // ROCm 7.2 compiler -- which tile depended on the schedule; scripts/diag/fused_bf_vs_fp32.hip.)
-    f32x4 acc6 = {0.f, 0.f, 0.f, 0.f};
-    {
-        const int o = 96 + lg * 4;
-        const bf16x4 w0 = *reinterpret_cast<const bf16x4*>(row0 + o);
-        const bf16x4 w1 = *reinterpret_cast<const bf16x4*>(row0 + BPLANE + o);
-        const bf16x4 w2 = *reinterpret_cast<const bf16x4*>(row0 + 2 * BPLANE + o);
-        acc6 = mfma16(w2, h6[0], acc6);
-        acc6 = mfma16(w1, h6[1], acc6);
-        acc6 = mfma16(w0, h6[2], acc6);
-        acc6 = mfma16(w1, h6[0], acc6);
-        acc6 = mfma16(w0, h6[1], acc6);
-        acc6 = mfma16(w0, h6[0], acc6);
-    }
-    return acc + acc6;
 }
 
 template <int ACT>
@@ -292,29 +248,8 @@ __device__ __forceinline__ float4 bf_epi(const float* bias, int t, int lg, const
     // per-tile lane offsets hipcc hoisted seven of them out of the layer loop and spilled them at 168 VGPRs, and
     // each reload's vmcnt(0) then also waited for this wave's earlier h stores (OOB + 64 t stays out of range)
     const uint32_t off = (t < 6 || lg == 0) ? ooff + 16u * lg : OOB;
-#if FWD_ABL & 1
-    asm volatile("" :: "v"(h.x), "v"(h.y), "v"(h.z), "v"(h.w));
-    (void)off;
-    (void)orsrc;
-#else
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, h), orsrc, off, 64 * t, 0);
-#endif
     return h;
-}
-
-template <int ACT>
-__device__ __forceinline__ void bf_layer(const __bf16* wb, const float* bias, const bf16x8 (&hp)[3][3],
-                                         const bf16x4 (&h6)[3], int lr, int lg, __amdgpu_buffer_rsrc_t orsrc,
-                                         uint32_t ooff, float4 (&hn)[7]) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-        const f32x4 a0 = bf_tile(wb, 2 * p, lr, lg, hp, h6);
-        const f32x4 a1 = bf_tile(wb, 2 * p + 1, lr, lg, hp, h6);
-        hn[2 * p] = bf_epi<ACT>(bias, 2 * p, lg, a0, orsrc, ooff);
-        hn[2 * p + 1] = bf_epi<ACT>(bias, 2 * p + 1, lg, a1, orsrc, ooff);
-    }
-    const f32x4 a6 = bf_tile(wb, 6, lr, lg, hp, h6);
-    hn[6] = bf_epi<ACT>(bias, 6, lg, a6, orsrc, ooff);
 }
 
 // fp32 h tiles (this lane: 4 columns 16t + 4lg of its row) -> the three bf16 B-operand planes
@@ -339,7 +274,7 @@ __device__ __forceinline__ void bf_split_operand(const float4 (&h)[7], bf16x8 (&
     }
 }
 
-// ---- f32 k tail (FWD_TAILF32): the 4-long k tail (features 96..99) as ONE exact 16x16x4 f32 MFMA that seeds
+// ---- f32 k tail: the 4-long k tail (features 96..99) as ONE exact 16x16x4 f32 MFMA that seeds
 // each tile's accumulator, instead of six 16x16x16 bf16 MFMAs -- which issue at 16 cycles each on gfx950, the
 // same as a 16x16x32 (scripts/diag/mfma_rate.hip): 6 x 16 = 96 -> 32 matrix cycles per tile. Its B operand
 // B[k = lg][m = lr] = h[m][96 + lg] must sit in lane (lr, lg): tile 6's A rows are W rows 96 + (lr >> 2)
@@ -359,7 +294,6 @@ __device__ __forceinline__ f32x4 tf_tile(const __bf16* wb, const float* wtail, i
     const int n = tf_row(t, lr);
     const __bf16* row0 = wb + n * BROW;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (FWD_ABL & 8) return __builtin_amdgcn_mfma_f32_16x16x4f32(wtail[4 * n + lg], h6, acc, 0, 0, 0);
 #pragma unroll
     for (int kb = 0; kb < 3; ++kb) {
         const int o = kb * 32 + lg * 8;
@@ -392,11 +326,7 @@ __device__ __forceinline__ void tf_layer(const __bf16* wb, const float* bias, co
     // tile 6: register 0 of lane (lr, lg) = pre-activation of h[lr][96 + lg]
     const f32x4 a6 = tf_tile(wb, wtail, 6, lr, lg, hp, h6);
     const float v = act_t<ACT>(a6[0] + bias[96 + lg]);
-#if FWD_ABL & 1
-    asm volatile("" :: "v"(v));
-#else
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), orsrc, ooff + 4u * lg, 4 * 96, 0);
-#endif
     hn[6].x = v;
 }
 
@@ -463,14 +393,9 @@ __device__ __forceinline__ void in0_layer(const FusedNet& N, const float* w0s, c
         else o6 = o;
     }
     // tile 6: lane (lr, 0) holds h[96..99]; the layer walk wants h[96 + lg] in register 0 of lane (lr, lg)
-    // (FWD_TAILF32), or the accumulator form itself (zeros beyond column 99)
-    if (FWD_TAILF32) {
-        const float v0 = __shfl(o6.x, lr, 64), v1 = __shfl(o6.y, lr, 64), v2 = __shfl(o6.z, lr, 64),
-                    v3 = __shfl(o6.w, lr, 64);
-        h[6] = float4{lg == 0 ? v0 : (lg == 1 ? v1 : (lg == 2 ? v2 : v3)), 0.f, 0.f, 0.f};
-    } else {
-        h[6] = o6;
-    }
+    const float v0 = __shfl(o6.x, lr, 64), v1 = __shfl(o6.y, lr, 64), v2 = __shfl(o6.z, lr, 64),
+                v3 = __shfl(o6.w, lr, 64);
+    h[6] = float4{lg == 0 ? v0 : (lg == 1 ? v1 : (lg == 2 ? v2 : v3)), 0.f, 0.f, 0.f};
 }
 
 #if FWD_STAMP
@@ -492,8 +417,7 @@ __device__ unsigned long long fw_real[FWS_WG][2][2];
 template <int NW, int ND = 0>
 __global__ __launch_bounds__((NW + ND) * 64, 1) void k_fwd_fused_bf(FusedArgs args) {
     constexpr int FTHREADS = NW * 64;
-    constexpr int FSLOTS = (FBLK4 + FTHREADS - 1) / FTHREADS;
-    extern __shared__ __attribute__((aligned(16))) unsigned char fsmb[];      // 2 x BBUF
+    extern __shared__ __attribute__((aligned(16))) unsigned char fsmb[];      // 2 x FWD_WIMG
     const int C = args.C;
     const int c = blockIdx.x % C;
     int item = blockIdx.x / C;
@@ -515,7 +439,7 @@ __global__ __launch_bounds__((NW + ND) * 64, 1) void k_fwd_fused_bf(FusedArgs ar
 #endif
     if (ND > 0 && wave >= NW) {
         // DMA waves: image 0 before the first barrier, image j + 1 after barrier j, each drained before the barrier
-        // that publishes it; the same barrier sequence as the compute waves (zero fill, one per layer, epilogue)
+        // that publishes it; the same barrier sequence as the compute waves (W0 staged, one per layer, epilogue)
         const unsigned char* wimgd = N.wimg + c * N.wimg_cs;
         for (int k = wave - NW; k < FWD_WIMG / 1024; k += ND)
             bf6::glds16_asm(wimgd + k * 1024 + lane * 16, fsmb + k * 1024);
@@ -524,7 +448,7 @@ __global__ __launch_bounds__((NW + ND) * 64, 1) void k_fwd_fused_bf(FusedArgs ar
         for (int j = 0; j < N.nl; ++j) {
             __syncthreads();
             FW_ST(j, 0)
-            if (j + 1 < N.nl && !(FWD_ABL & 4)) {
+            if (j + 1 < N.nl) {
                 for (int k = wave - NW; k < FWD_WIMG / 1024; k += ND)
                     bf6::glds16_asm(wimgd + (int64_t)(j + 1) * FWD_WIMG + k * 1024 + lane * 16,
                                     fsmb + ((j + 1) & 1) * FWD_WIMG + k * 1024);
@@ -537,69 +461,14 @@ __global__ __launch_bounds__((NW + ND) * 64, 1) void k_fwd_fused_bf(FusedArgs ar
         return;
     }
 
-    // zero the never-written tail columns 100..111 of every plane row and the bias pad, both buffers
-    // (register staging only: the pre-split images carry their zeros)
-    if (!N.wimg) {
-        for (int i = tid; i < 2 * 3 * FW; i += FTHREADS) {
-            __bf16* r = reinterpret_cast<__bf16*>(fsmb + (i / (3 * FW)) * BBUF) + (i % (3 * FW)) * BROW + 100;
-#pragma unroll
-            for (int z = 0; z < 12; ++z) r[z] = (__bf16)0.f;
-        }
-        if (tid < 24) reinterpret_cast<float*>(fsmb + (tid / 12) * BBUF + 3 * BPLANE * 2)[100 + tid % 12] = 0.f;
-    }
-
-    // staging slot v: float4 i of [W | bias] -> (plane row position) or bias position
-    int sdst[FSLOTS];
-#pragma unroll
-    for (int v = 0; v < FSLOTS; ++v) {
-        const int i = tid + FTHREADS * v;
-        if (i < FW * FW / 4) {
-            const int n = i / (FW / 4), c4 = i % (FW / 4), tq = c4 >> 2, g = c4 & 3;
-            const int pos = tq < 6 ? (tq >> 1) * 32 + g * 8 + (tq & 1) * 4 : 96 + g * 4;
-            sdst[v] = n * BROW + pos;                     // bf16 index within a plane
-        } else {
-            sdst[v] = i < FBLK4 ? -1 - 4 * (i - FW * FW / 4) : INT32_MIN;   // bias float index, encoded
-        }
-    }
-    f32x4 pf[FSLOTS];
-#define VIHMC_FB_LOAD(J)                                                                              \
-    {                                                                                                 \
-        const f32x4* src = reinterpret_cast<const f32x4*>(Wc + N.w_off[J]);                           \
-        _Pragma("unroll") for (int v = 0; v < FSLOTS; ++v)                                            \
-            pf[v] = src[min(tid + FTHREADS * v, FBLK4 - 1)];                                          \
-    }
-#define VIHMC_FB_STORE(BUF)                                                                           \
-    _Pragma("unroll") for (int v = 0; v < FSLOTS; ++v) {                                              \
-        unsigned char* bb = fsmb + (BUF) * BBUF;                                                      \
-        if (sdst[v] >= 0) {                                                                           \
-            bf16x4 a, b, cc;                                                                          \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                           \
-                __bf16 x0, x1, x2;                                                                    \
-                split3(pf[v][j], x0, x1, x2);                                                         \
-                a[j] = x0; b[j] = x1; cc[j] = x2;                                                     \
-            }                                                                                         \
-            __bf16* pl = reinterpret_cast<__bf16*>(bb) + sdst[v];                                     \
-            *reinterpret_cast<bf16x4*>(pl) = a;                                                       \
-            *reinterpret_cast<bf16x4*>(pl + BPLANE) = b;                                              \
-            *reinterpret_cast<bf16x4*>(pl + 2 * BPLANE) = cc;                                         \
-        } else if (sdst[v] != INT32_MIN) {                                                            \
-            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(bb + 3 * BPLANE * 2) + (-1 - sdst[v])) = pf[v]; \
-        }                                                                                             \
-    }
-
     // pre-split weight images (k_split_wimg): layer j's image is DMA-copied into buffer j&1 one layer ahead
     // (global_load_lds, 1 KB per wave-instruction, no VGPRs / VALU); the barrier drains it (vmcnt(0))
-    const bool dma = FWD_TAILF32 || FWD_DMA_ONLY || N.wimg != nullptr;  // FWD_TAILF32: images only (host-checked)
-    const unsigned char* wimgc = dma ? N.wimg + c * N.wimg_cs : nullptr;
+    const unsigned char* wimgc = N.wimg + c * N.wimg_cs;     // never null (launch_fwd_fused_bf checks)
 #define VIHMC_FB_DMA(J, BUF)                                                                          \
     if (ND == 0)                                                                                      \
     for (int k = wave; k < FWD_WIMG / 1024; k += NW)                                                  \
         bf6::glds16_asm(wimgc + (int64_t)(J) * FWD_WIMG + k * 1024 + lane * 16, fsmb + (BUF) * FWD_WIMG + k * 1024);
-    if (dma) {
-        VIHMC_FB_DMA(0, 0)
-    } else {
-        VIHMC_FB_LOAD(0)
-    }
+    VIHMC_FB_DMA(0, 0)
     float4 h[7];
     float4 xa[6];
     float xt[4];
@@ -628,13 +497,9 @@ __global__ __launch_bounds__((NW + ND) * 64, 1) void k_fwd_fused_bf(FusedArgs ar
         const float* ar = N.in + c * N.in_cs + (int64_t)rowc * N.ldin;
 #pragma unroll
         for (int t = 0; t < 6; ++t) h[t] = *reinterpret_cast<const float4*>(ar + 16 * t + 4 * lg);
-        if (FWD_TAILF32) h[6] = float4{ar[96 + lg], 0.f, 0.f, 0.f};
-        else h[6] = lg == 0 ? *reinterpret_cast<const float4*>(ar + 96) : float4{0.f, 0.f, 0.f, 0.f};
+        h[6] = float4{ar[96 + lg], 0.f, 0.f, 0.f};
     }
-    __syncthreads();                            // zero fill done before the staging writes (and W0 staged)
-    if (!dma) {
-        VIHMC_FB_STORE(0)
-    }
+    __syncthreads();                            // W0 staged
     __builtin_amdgcn_s_waitcnt(0x0F70);         // see k_fwd_fused: no vmcnt waits inside the layer loop
     if (N.x != nullptr) {
         float* h0 = const_cast<float*>(N.in) + c * N.in_cs;
@@ -648,54 +513,35 @@ __global__ __launch_bounds__((NW + ND) * 64, 1) void k_fwd_fused_bf(FusedArgs ar
     for (int j = 0; j < N.nl; ++j) {
         __syncthreads();
         FW_ST(j, 0)
-        if (dma) {
-            if (j + 1 < N.nl) {
-                VIHMC_FB_DMA(j + 1, (j + 1) & 1)
-            }
-        } else {
-            VIHMC_FB_LOAD(min(j + 1, N.nl - 1))
+        if (j + 1 < N.nl) {
+            VIHMC_FB_DMA(j + 1, (j + 1) & 1)
         }
-        const unsigned char* bbuf = fsmb + (j & 1) * (dma ? FWD_WIMG : BBUF);
+        const unsigned char* bbuf = fsmb + (j & 1) * FWD_WIMG;
         const __bf16* wb = reinterpret_cast<const __bf16*>(bbuf);
         const float* bias = reinterpret_cast<const float*>(bbuf + 3 * BPLANE * 2);
         const __amdgpu_buffer_rsrc_t orsrc = make_rsrc(outc + N.h_off[j], obytes);
         const uint32_t hoffj = (N.skip_last && j == N.nl - 1) ? OOB : ooff;   // stores issued, dropped (vmcnt count)
         bf16x8 hp[3][3];
         const int act = N.act[j];
-        if (FWD_TAILF32) {
-            bf16x4 h6u[3];
-            bf_split_operand(h, hp, h6u);          // tile 6 planes unused (the f32 MFMA takes h[6].x)
+        bf16x4 h6u[3];
+        bf_split_operand(h, hp, h6u);          // tile 6 planes unused (the f32 MFMA takes h[6].x)
 #if FWD_STAMP
-            __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #endif
-            FW_ST(j, 1)
-            const float* wtail = reinterpret_cast<const float*>(bbuf + FWD_WTAIL);
-            const float h6f = h[6].x;
-            if (act == ACT_TANH) tf_layer<ACT_TANH>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
-            else if (act == ACT_TANH_CR) tf_layer<ACT_TANH_CR>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
-            else if (act == ACT_RELU) tf_layer<ACT_RELU>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
-            else tf_layer<ACT_ID>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
+        FW_ST(j, 1)
+        const float* wtail = reinterpret_cast<const float*>(bbuf + FWD_WTAIL);
+        const float h6f = h[6].x;
+        if (act == ACT_TANH) tf_layer<ACT_TANH>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
+        else if (act == ACT_TANH_CR) tf_layer<ACT_TANH_CR>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
+        else if (act == ACT_RELU) tf_layer<ACT_RELU>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
+        else tf_layer<ACT_ID>(wb, bias, wtail, hp, h6f, lr, lg, orsrc, hoffj, h);
 #if FWD_STAMP
-            __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
 #endif
-            FW_ST(j, 2)
-        } else {
-            bf16x4 h6[3];
-            bf_split_operand(h, hp, h6);
-            if (act == ACT_TANH) bf_layer<ACT_TANH>(wb, bias, hp, h6, lr, lg, orsrc, hoffj, h);
-            else if (act == ACT_TANH_CR) bf_layer<ACT_TANH_CR>(wb, bias, hp, h6, lr, lg, orsrc, hoffj, h);
-            else if (act == ACT_RELU) bf_layer<ACT_RELU>(wb, bias, hp, h6, lr, lg, orsrc, hoffj, h);
-            else bf_layer<ACT_ID>(wb, bias, hp, h6, lr, lg, orsrc, hoffj, h);
-        }
-        if (!dma) {
-            VIHMC_FB_STORE((j + 1) & 1)
-        }
+        FW_ST(j, 2)
         // layer j+1's image landed before the next barrier. The DMA was issued ahead of this layer's seven h stores
         // (six b128 + the tile-6 b32), so a counted wait leaves those stores in flight (vmcnt(0) waited for them)
-        if (dma) {
-            if (FWD_TAILF32) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-            else bf6::wait_vmcnt0();
-        }
+        asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
         FW_ST(j, 3)
     }
 #if FWD_STAMP
@@ -781,13 +627,12 @@ __global__ __launch_bounds__((NW + ND) * 64, 1) void k_fwd_fused_bf(FusedArgs ar
                 *reinterpret_cast<u32x4*>(blk + off) = *reinterpret_cast<const u32x4*>(reg + i * 16);
         }
     }
-#undef VIHMC_FB_LOAD
-#undef VIHMC_FB_STORE
 #undef VIHMC_FB_DMA
 }
 
 // [W_j | bias_j] of every fused layer of every chain -> the LDS image k_fwd_fused_bf stages (same permuted
-// column order as VIHMC_FB_STORE, zero padding, bias fp32 [112]); one block per (chain, net, layer)
+// column order the bf16 MFMA's k slots want (see the block comment above), zero padding, bias fp32 [112]); one block
+// per (chain, net, layer)
 __global__ __launch_bounds__(1024) void k_split_wimg(FusedArgs args) {
     const int C = args.C;
     int b = blockIdx.x;
@@ -802,7 +647,8 @@ __global__ __launch_bounds__(1024) void k_split_wimg(FusedArgs args) {
     for (int i = threadIdx.x; i < FW * 112 / 4; i += 1024) {          // plane positions, 4 at a time
         const int n = i / 28, q = i % 28;                            // row n, positions 4q..4q+3
         const int pos = 4 * q;
-        // inverse of VIHMC_FB_STORE's map: position -> source column
+        // position -> source column: k-block kb = pos / 32 holds, per lane group g, 4 columns of tile 2kb then 4 of
+        // tile 2kb + 1 (slots 8g .. 8g + 7); the tail positions 96.. are the columns themselves
         int col;
         if (pos < 96) {
             const int kb = pos >> 5, g = (pos & 31) >> 3, hi = (pos >> 2) & 1;
@@ -827,7 +673,7 @@ __global__ __launch_bounds__(1024) void k_split_wimg(FusedArgs args) {
     }
     float* bias = reinterpret_cast<float*>(img + 3 * BPLANE * 2);
     for (int i = threadIdx.x; i < 112; i += 1024) bias[i] = i < FW ? src[FW * FW + i] : 0.f;
-    // fp32 k tail W[n][96..99] (FWD_TAILF32), then zeros to the end of the image
+    // fp32 k tail W[n][96..99], then zeros to the end of the image
     float* wtail = reinterpret_cast<float*>(img + FWD_WTAIL);
     for (int i = threadIdx.x; i < FW * 4; i += 1024) wtail[i] = src[(i >> 2) * FW + 96 + (i & 3)];
     for (int i = FWD_WTAIL + FW * 16 + threadIdx.x * 4; i < FWD_WIMG; i += 1024 * 4)
@@ -840,7 +686,7 @@ hipError_t launch_split_wimg(const FusedArgs& a, hipStream_t s) {
 }
 
 int fwd_img_plane_off(int n, int col) {
-    // inverse of k_split_wimg's position -> column map (VIHMC_FB_STORE's permuted column order)
+    // inverse of k_split_wimg's position -> column map
     const int t = col >> 4, g = (col >> 2) & 3, e = col & 3;
     const int pos = t < 6 ? (t >> 1) * 32 + g * 8 + (t & 1) * 4 + e : 96 + g * 4 + e;
     return 2 * (n * BROW + pos);
@@ -852,13 +698,12 @@ int fwd_img_tail_off(int n, int col) { return FWD_WTAIL + 4 * (n * 4 + (col - 96
 size_t fwd_fused_bf_lds_bytes() { return 2 * (size_t)FWD_WIMG; }
 static_assert(BBUF <= FWD_WIMG && FWD_WTAIL + FW * 16 <= FWD_WIMG && FWD_WIMG % 1024 == 0 &&
               2 * FWD_WIMG <= 160 * 1024, "weight image");
-bool fwd_fused_bf_needs_wimg() { return FWD_TAILF32 != 0; }
 
 // an input layer [100][n_in] (x row stride ldx, W0 row stride ldw) the bf16x6 forward can run in its launch (the
-// pre-split-image form: FWD_TAILF32; W0 staged in one image buffer; its tanh the row-dot epilogue's)
+// pre-split-image form; W0 staged in one image buffer; its tanh the row-dot epilogue's)
 bool fwd_fused_in0_ok(int n_in, int ldx, int ldw) {
     const int k4 = (n_in + 3) & ~3;
-    return FWD_TAILF32 && FWD_ABL == 0 && n_in >= 1 && n_in <= IN0_KMAX && ldx >= k4 &&
+    return n_in >= 1 && n_in <= IN0_KMAX && ldx >= k4 &&
            (n_in < 16 || (ldx & 3) == 0) && ldw >= k4 && (ldw & 3) == 0 &&
            (size_t)FW * in0_ldw(k4) * sizeof(float) <= (size_t)FWD_WIMG;
 }
@@ -875,11 +720,11 @@ int fwd_fused_bf_waves() { return FWD_BF_NW; }
 
 hipError_t launch_fwd_fused_bf(const FusedArgs& a, int nw, hipStream_t s) {
     dim3 g(a.C * (a.net[0].nblk + a.net[1].nblk));
+    // the kernel reads its weights from the pre-split images only
+    if (!a.net[0].wimg || !a.net[1].wimg) return hipErrorInvalidValue;
     // 4 waves (64 rows per workgroup) for chain counts whose 12-wave grid would leave most CUs idle (single chain:
-    // 176 workgroups instead of 60)
-    if (nw == 4 && FWD_TAILF32 && a.net[0].wimg && a.net[1].wimg)
-        hipLaunchKernelGGL((k_fwd_fused_bf<4, 4>), g, dim3(8 * 64), fwd_fused_bf_lds_bytes(), s, a);
-    else if (nw == 4) hipLaunchKernelGGL(k_fwd_fused_bf<4>, g, dim3(4 * 64), fwd_fused_bf_lds_bytes(), s, a);
+    // 176 workgroups instead of 60), with 4 DMA waves beside them
+    if (nw == 4) hipLaunchKernelGGL((k_fwd_fused_bf<4, 4>), g, dim3(8 * 64), fwd_fused_bf_lds_bytes(), s, a);
     else hipLaunchKernelGGL(k_fwd_fused_bf<FWD_BF_NW>, g, dim3(FWD_BF_NW * 64), fwd_fused_bf_lds_bytes(), s, a);
     return hipGetLastError();
 }

@@ -30,7 +30,6 @@
 // YA = y[n][p] and YB = y^T[p][n] store each 32-long k block in that order, so a lane's A fragment is one 16-B load.
 #include "vihmc_internal.h"
 #include "vihmc_bf16x6.h"
-#include <type_traits>
 
 namespace vihmc {
 
@@ -72,7 +71,7 @@ __host__ __device__ inline int kpos(int k) { return k < 16 ? 8 * (k >> 2) + (k &
 // iteration i (every wave is past block i-1 = buffer (i+2) % 3), then wait for block i+1 (21 newer copies may stay
 // in flight) so the next barrier publishes it. SRC(i) gives block i's global address.
 #define GRAM_DMA_PIECES(SRC, BUF)                                                                             \
-    for (int k = 0; k < (GR_ABL & 2 ? 0 : GR_PIECES); ++k)                                                     \
+    for (int k = 0; k < GR_PIECES; ++k)                                                                       \
         bf6::glds16_asm((SRC) + k * 1024 + lane * 16, lds + (BUF) * GR_BLK + k * 1024);
 
 struct NoStamp {
@@ -112,8 +111,8 @@ __device__ __forceinline__ void dma_role2(unsigned char* lds, int lane, int nb, 
         const unsigned char* a = s0 + (int64_t)i * CONTRACT_SPLIT_BLOCK;
         const unsigned char* b = s1 + (int64_t)i * CONTRACT_SPLIT_BLOCK;
         unsigned char* d = lds + (i % GR_NBUF) * 2 * GR_BLK;
-        for (int k = 0; k < (GR_ABL & 2 ? 0 : GR_PIECES); ++k) bf6::glds16_asm(a + k * 1024 + lane * 16, d + k * 1024);
-        for (int k = 0; k < (GR_ABL & 2 ? 0 : GR_PIECES); ++k)
+        for (int k = 0; k < GR_PIECES; ++k) bf6::glds16_asm(a + k * 1024 + lane * 16, d + k * 1024);
+        for (int k = 0; k < GR_PIECES; ++k)
             bf6::glds16_asm(b + k * 1024 + lane * 16, d + GR_BLK + k * 1024);
     };
     if (nb > 0) issue(0);
@@ -404,7 +403,7 @@ __global__ __launch_bounds__(GR_THREADS, 1) void k_gram_a(GramArgs A) {
         const int64_t rt16 = 16 * (int64_t)A.ya_ld;
         bf16x8 a0[2][3], a1[2][3];
         auto load_a = [&](bf16x8 (&a)[2][3], int i) __attribute__((always_inline)) {
-            const int ii = (GR_ABL & 1) ? 0 : min(i, nb - 1);
+            const int ii = min(i, nb - 1);
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -436,7 +435,7 @@ __global__ __launch_bounds__(GR_THREADS, 1) void k_gram_a(GramArgs A) {
         auto step = [&](int i, bf16x8 (&a)[2][3], bf16x8 (&an)[2][3]) __attribute__((always_inline)) {
             __syncthreads();
             GR_ST(i, 0)
-            const int ii = (GR_ABL & 1) ? 0 : min(i + 1, nb - 1);
+            const int ii = min(i + 1, nb - 1);
             GR_ST(i, 1)
             const unsigned char* buf = lds + (i % GR_NBUF) * GR_BLK;
             // the next block's A loads, one per tile under this block's MFMAs
@@ -693,7 +692,7 @@ __global__ __launch_bounds__(GR_THREADS, 1) void k_gram_b(GramArgs A) {
         const int64_t rt16 = 16 * (int64_t)A.yb_ld;
         bf16x8 a0[2][3], a1[2][3];
         auto load_a = [&](bf16x8 (&a)[2][3], int i) __attribute__((always_inline)) {
-            const int ii = (GR_ABL & 1) ? 0 : min(i, nbm - 1);
+            const int ii = min(i, nbm - 1);
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -706,7 +705,7 @@ __global__ __launch_bounds__(GR_THREADS, 1) void k_gram_b(GramArgs A) {
             for (int t = 0; t < 7; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
         auto step = [&](int i, bf16x8 (&a)[2][3], bf16x8 (&an)[2][3]) __attribute__((always_inline)) {
             __syncthreads();
-            const int ii = (GR_ABL & 1) ? 0 : min(i + 1, nbm - 1);
+            const int ii = min(i + 1, nbm - 1);
             // the next block's A loads, one per tile under this block's MFMAs (see mma_block)
             mma_block(lds + (i % GR_NBUF) * GR_BLK, tro, a, acc, [&](int t) __attribute__((always_inline)) {
                 if (t < 6) {
@@ -1137,8 +1136,7 @@ __device__ __forceinline__ void dzb_unit(const GramArgs& A, int u, unsigned char
     float* out = A.dzb + c * A.dzb_cs;
     for (int tile = wv; tile < 14; tile += GR_THREADS / 64) {
         const int rt = tile / 7, t = tile - rt * 7;
-        using acc_t = std::conditional_t<GRAM_DZB_FP64 != 0, double, float>;
-        acc_t ts[4] = {0, 0, 0, 0};
+        double ts[4] = {0, 0, 0, 0};          // the T_b slabs and Zb^ Gt summed in fp64
         int ss = 0;
         for (; ss + 8 <= nslab; ss += 8) {                // eight slab loads in flight, then the adds in order
             f32x4 v[8];
@@ -1147,26 +1145,26 @@ __device__ __forceinline__ void dzb_unit(const GramArgs& A, int u, unsigned char
 #pragma unroll
             for (int k = 0; k < 8; ++k)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) ts[r] += (acc_t)v[k][r];
+                for (int r = 0; r < 4; ++r) ts[r] += (double)v[k][r];
         }
         for (; ss < nslab; ++ss) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(tb + ss * sstride + tile * 256);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) ts[r] += (acc_t)v[r];
+            for (int r = 0; r < 4; ++r) ts[r] += (double)v[r];
         }
-        acc_t gz[4] = {0, 0, 0, 0};
+        double gz[4] = {0, 0, 0, 0};
         const int x = 16 * t + lr;
         for (int v = 0; v < 101; ++v) {
             const f32x4 z = *reinterpret_cast<const f32x4*>(zbt + v * 32 + 16 * rt + 4 * lg);
-            const acc_t g = (acc_t)gts[v * 112 + x];     // fp64 Gt (with GRAM_DZB_FP64 = 0 rounded to fp32)
+            const double g = gts[v * 112 + x];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) gz[r] = fma((acc_t)z[r], g, gz[r]);
+            for (int r = 0; r < 4; ++r) gz[r] = fma((double)z[r], g, gz[r]);
         }
         if (x < 100) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int n = n32 + 16 * rt + 4 * lg + r;
-                if (n < A.N) out[(int64_t)n * A.ldz + x] = (float)((acc_t)A.gscale * (gz[r] - ts[r]));
+                if (n < A.N) out[(int64_t)n * A.ldz + x] = (float)((double)A.gscale * (gz[r] - ts[r]));
             }
         }
     }

@@ -474,14 +474,14 @@ int fwd_img_plane_off(int n, int col);
 int fwd_img_plane_stride();
 int fwd_img_bias_off(int n);
 int fwd_img_tail_off(int n, int col);
-bool fwd_fused_bf_needs_wimg();                     // the bf16x6 forward reads the fp32 k tail of the image
 bool fwd_fused_in0_ok(int n_in, int ldx, int ldw);  // an input layer of this shape fits the fused forward
 int fwd_fused_bf_waves();                           // its waves per workgroup (16 rows each)
-// VIHMC_DIAG (vihmc_diag.h): nonzero in a build with timing-only ablations (wrong results) or phase stamps.
+// VIHMC_DIAG (vihmc_diag.h): nonzero in an instrumented build (in-kernel phase stamps, which perturb timing).
 // vihmc_version() reports it and plan creation refuses such a library unless VIHMC_ALLOW_DIAG=1.
 int diag_switches();
 hipError_t launch_fwd_fused(const FusedArgs& a, int nwaves, hipStream_t s);   // nwaves: 12 or 4
-hipError_t launch_fwd_fused_bf(const FusedArgs& a, int nw, hipStream_t s);     // bf16x6, 12 (or 4) waves
+// bf16x6, 12 (or 4) waves; hipErrorInvalidValue without both nets' weight images (FusedNet::wimg)
+hipError_t launch_fwd_fused_bf(const FusedArgs& a, int nw, hipStream_t s);
 
 size_t fwd_fused_lds_bytes();
 

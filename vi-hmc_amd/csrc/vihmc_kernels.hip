@@ -454,10 +454,10 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather_prior(const float* gp
                 } else {
                     const float step = lf.inv_mass ? (e * imv[u]) * pn : e * pn;
                     const float tn = th + step;
-                    if (!(GATHER_ABL & 2)) lf.th[o] = tn;
-                    if (scat && !GATHER_ABL) scatter_store(lf.sc.packed, lf.sc.dp, lf.sc.si, c, sx[u], tn);
+                    lf.th[o] = tn;
+                    if (scat) scatter_store(lf.sc.packed, lf.sc.dp, lf.sc.si, c, sx[u], tn);
                 }
-                if (!(GATHER_ABL & 2)) lf.p[o] = pn;
+                lf.p[o] = pn;
             }
         }
     }

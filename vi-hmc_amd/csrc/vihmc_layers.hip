@@ -582,7 +582,7 @@ bool rowdot_in_ok(const RowdotArgs& a, int nt) {
 
 template <int MS, int MODE>
 static hipError_t rowdot_nt(const RowdotArgs& a, int nt, hipStream_t s) {
-    const int blocks = a.C * a.p[0].tiles + (a.nprob > 1 && !RD_ONLY_FIRST ? a.C * a.p[1].tiles : 0);
+    const int blocks = a.C * a.p[0].tiles + (a.nprob > 1 ? a.C * a.p[1].tiles : 0);
     const size_t shm = rowdot_lds_bytes(a);
     dim3 g(blocks), blk(256);
     const bool k100 = a.p[0].K == 100 && (a.nprob < 2 || a.p[1].K == 100);

@@ -410,8 +410,8 @@ int check_lik(const vihmc_lik_desc& l) {
     if (vihmc::diag_switches()) {
         const char* e = std::getenv("VIHMC_ALLOW_DIAG");
         if (!(e && e[0] == '1'))
-            return fail(std::string("library built with timing-only diagnostic switches (") + vihmc_version() +
-                        "): results are wrong by design; set VIHMC_ALLOW_DIAG=1 for A/B timing only");
+            return fail(std::string("instrumented build (") + vihmc_version() +
+                        "): its phase stamps perturb timing; set VIHMC_ALLOW_DIAG=1 for the stamp readers only");
     }
     if (l.loss != VIHMC_LOSS_NLL && l.loss != VIHMC_LOSS_REGRESSION) return fail("unsupported loss kind");
     if (!(l.prior_scale > 0.f)) return fail("prior_scale must be > 0");
@@ -1142,7 +1142,6 @@ inline int rowdot_tpw(int64_t total_tiles) {
 // Layers 1..L-1 of both nets can run in the fused register-resident forward (vihmc_fused.hip) when they
 // are all 100 -> 100 with the packed [W | bias] block contiguous.
 bool fused_forward_ok(const vihmc_plan* p) {
-    if (!VIHMC_FUSED_FWD) return false;
     for (int net = 0; net < 2; ++net) {
         const Net& n = p->nets[net];
         const int nl = (int)n.L.size();
@@ -1184,6 +1183,8 @@ void fused_args(vihmc_plan* p, int C, FusedArgs& a) {
         }
         f.rows = n.rows;
     }
+    // pre-split weight images (FWD_WIMG bytes per fused layer; null when the plan has none): the bf16x6 forward
+    // DMA-stages them, the fp32 forward never reads them
     a.net[0].wimg = p->wimg;
     a.net[1].wimg = p->wimg ? p->wimg + (int64_t)a.net[0].nl * FWD_WIMG : nullptr;
     a.net[0].wimg_cs = a.net[1].wimg_cs = p->wimg_cs;
@@ -1192,7 +1193,7 @@ void fused_args(vihmc_plan* p, int C, FusedArgs& a) {
 // the input layers of both nets can run inside the bf16x6 forward's launch (FusedNet::x): the pre-split-image form
 // and an input layer of a shape it stages
 bool fused_input_ok(const vihmc_plan* p) {
-    if (!p->fwd_bf16x6 || !p->fwd_wimg || !p->wimg || !fwd_fused_bf_needs_wimg() || !p->fwd_in0) return false;
+    if (!p->fwd_bf16x6 || !p->fwd_wimg || !p->wimg || !p->fwd_in0) return false;
     if ((p->dp & 3) != 0) return false;
     for (int net = 0; net < 2; ++net) {
         const Net& n = p->nets[net];
@@ -1219,13 +1220,12 @@ int launch_forward_fused(vihmc_plan* p, int C, hipStream_t s, bool img, bool in0
             f.b0_off = L.bias;
         }
     }
-    a.net[0].wimg = a.net[1].wimg = nullptr;           // set below when the bf16x6 kernel stages them
     // 12-wave workgroups (one per CU, 84 KB LDS) unless that grid would leave most of the 256 CUs idle
     const int64_t blocks12 = (int64_t)C * (cdiv(p->nets[0].rows, 192) + cdiv(p->nets[1].rows, 192));
     const int nw = blocks12 >= 192 ? 12 : 4;
     // bf16x6 at 12 waves, or at 4 for small chain counts
     const int nwb = nw == 12 ? fwd_fused_bf_waves() : 4;
-    if (p->fwd_bf16x6 && (!fwd_fused_bf_needs_wimg() || (p->fwd_wimg && p->wimg))) {
+    if (p->fwd_bf16x6 && p->fwd_wimg && p->wimg) {
         for (int net = 0; net < 2; ++net) a.net[net].nblk = cdiv(p->nets[net].rows, 16 * nwb);
         if (img) {
             // the contraction's pre-split images of the branch (side A) and trunk (side B) outputs
@@ -1242,18 +1242,13 @@ int launch_forward_fused(vihmc_plan* p, int C, hipStream_t s, bool img, bool in0
             a.net[1].skip_last = gram_only && p->skip_zt ? 1 : 0;
             p->img_by_fwd = true;
         }
-        if (p->fwd_wimg && p->wimg) {
-            // pre-split weight images, DMA-staged by the forward (FWD_WIMG bytes per fused layer); kept current by the
-            // scatter when the plan built its image maps, else split here from the packed weights
-            a.net[0].wimg = p->wimg;
-            a.net[1].wimg = p->wimg + (int64_t)a.net[0].nl * FWD_WIMG;
-            a.net[0].wimg_cs = a.net[1].wimg_cs = p->wimg_cs;
-            if (!p->img_by_scatter) {
-                HIPCHK(launch_split_wimg(a, s));
-                if (p->wtimg) {
-                    HIPCHK(launch_split_wtimg(a, p->wtimg, p->wtimg_cs, s));
-                    p->timg_live = true;
-                }
+        // the weight images (fused_args) are kept current by the scatter when the plan built its image maps, else
+        // split here from the packed weights
+        if (!p->img_by_scatter) {
+            HIPCHK(launch_split_wimg(a, s));
+            if (p->wtimg) {
+                HIPCHK(launch_split_wtimg(a, p->wtimg, p->wtimg_cs, s));
+                p->timg_live = true;
             }
         }
         HIPCHK(launch_fwd_fused_bf(a, nwb, s));

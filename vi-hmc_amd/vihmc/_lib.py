@@ -109,9 +109,9 @@ def lib() -> ctypes.CDLL:
                 f.argtypes = args
             ver = L.vihmc_version().decode()
             if not re.search(r"diag=0(\s|$)", ver) and os.environ.get("VIHMC_ALLOW_DIAG") != "1":
-                raise RuntimeError(f"{LIB_PATH} was built with timing-only diagnostic switches ({ver}); its results "
-                                   "are wrong by design. Rebuild without EXTRA=-D*_ABL/-D*_STAMP, or set "
-                                   "VIHMC_ALLOW_DIAG=1 for A/B timing only")
+                raise RuntimeError(f"{LIB_PATH} is an instrumented build ({ver}); its phase stamps perturb timing. "
+                                   "Rebuild without EXTRA=-DVIHMC_DIAG=..., or set VIHMC_ALLOW_DIAG=1 for the stamp "
+                                   "readers only")
             _lib = L
     return _lib
 
