@@ -93,16 +93,12 @@ __device__ unsigned long long bb_real[BBS_WG][2][2];
 #endif
 constexpr int BBS_NONE = 1 << 20;                      // stamp index of the prologue's h stage: never recorded
 
-__global__ __launch_bounds__(BB_THREADS, 1) void k_bwd_bf2(BwdArgs args) {
+// One layer of one (net, chain, row chunk): the whole workgroup, every role. b = the block's index inside its net
+// (c * n_wg + wg), second = the launch's second net (both only pick the diagnostic stamps' workgroups).
+__device__ __forceinline__ void bwd_bf2_layer(const BwdProb& P, const int c, const int wg, const int b, const bool second,
+                                              const int tid) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smw[];
-    int b = blockIdx.x;
-    const int per0 = args.C * args.p[0].n_wg;
-    const bool second = b >= per0;
-    const BwdProb P = second ? args.p[1] : args.p[0];
-    if (second) b -= per0;
-    const int c = b / P.n_wg;
-    const int wg = b - c * P.n_wg;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lg = lane >> 4;
+    const int wave = tid >> 6, lane = tid & 63, lr = lane & 15, lg = lane >> 4;
     const int NI4 = (P.n_in + 3) & ~3;
     const int hq4 = NI4 >> 2;                          // H float4 per row (<= 27)
     const float* D = P.D + c * P.d_cs;
@@ -510,6 +506,51 @@ __global__ __launch_bounds__(BB_THREADS, 1) void k_bwd_bf2(BwdArgs args) {
 #endif
 }
 
+__global__ __launch_bounds__(BB_THREADS, 1) void k_bwd_bf2(BwdArgs args) {
+    int b = blockIdx.x;
+    const int per0 = args.C * args.p[0].n_wg;
+    const bool second = b >= per0;
+    const BwdProb P = second ? args.p[1] : args.p[0];
+    if (second) b -= per0;
+    const int c = b / P.n_wg;
+    bwd_bf2_layer(P, c, b - c * P.n_wg, b, second, threadIdx.x);
+}
+
+// Layers nl - 1 .. 1 of the workgroup's own row chunk in one launch. The backward is row-independent: workgroup
+// (net, chain, chunk) of layer j - 1 reads exactly the delta rows the same workgroup wrote in layer j (every layer
+// j >= 1 of a net has the same chunks, bwd_layers_ok), so nothing crosses workgroups and no grid-wide ordering is
+// needed. The deltas still round-trip through global memory, delta[0] <-> delta[1] as the per-layer launches
+// alternate them, and every layer runs bwd_bf2_layer on the descriptor its own launch would get: the same products
+// in the same order into the same slabs.
+// Layer boundary: the dX waves (the only ones that store deltas) wait for their stores, then one workgroup barrier;
+// the next layer's staging loads are issued after it by waves of the same CU, through the same vector L1, so they
+// read the stored rows. The barrier also orders the last reads of the LDS buffers and of the W^T planes (dX and dW
+// waves, sub-tile nsub - 1) before the next layer's prologue rewrites them. The dW waves' slab stores are not waited
+// for: nothing reads the slabs before the reduce launch. A layer's prefetches past the chunk's end land in
+// registers that no store uses, and the next layer starts its register sets afresh after the barrier.
+__global__ __launch_bounds__(BB_THREADS, 1) void k_bwd_bf2_layers(BwdLayersArgs args) {
+    int b = blockIdx.x;
+    const int per0 = args.C * args.p[0][0].n_wg;
+    const int net = b >= per0 ? 1 : 0;
+    if (net) b -= per0;
+    const int n_wg = args.p[net][0].n_wg;
+    const int c = b / n_wg;
+    const int wg = b - c * n_wg;
+    const int nk = args.nk[net];
+    for (int k = 0; k < nk; ++k) {
+        if (k) {
+            if (threadIdx.x < 512) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+        // the thread index opaque per layer: nothing a role derives from it is hoisted out of the layer loop, where it
+        // would stay live through the other roles' bodies (16 VGPRs spilled at the 128 of four waves per SIMD)
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        __builtin_assume(tid >= 0 && tid < BB_THREADS);
+        bwd_bf2_layer(args.p[net][k], c, wg, b, net != 0, tid);
+    }
+}
+
 bool bwd_bf_ok(const BwdArgs& a) {
     for (int i = 0; i < a.nprob; ++i) {
         const BwdProb& p = a.p[i];
@@ -529,6 +570,30 @@ extern "C" int vihmc_debug_bb_stamps(void* stamps, size_t stamp_bytes, void* rea
     return (int)e;
 }
 #endif
+
+bool bwd_layers_ok(const BwdLayersArgs& a) {
+    for (int net = 0; net < 2; ++net) {
+        if (a.nk[net] < 1 || a.nk[net] > BWD_LAYERS_MAXK) return false;
+        for (int k = 0; k < a.nk[net]; ++k) {
+            const BwdProb& q = a.p[net][k];
+            BwdArgs one{};
+            one.p[0] = q;
+            one.nprob = 1;
+            if (!q.has_dx || !bwd_bf_ok(one)) return false;
+            if (q.rows_per_wg != a.p[net][0].rows_per_wg || q.n_wg != a.p[net][0].n_wg || q.M != a.p[net][0].M) return false;
+            // layer k reads the rows layer k - 1 wrote, at the same chain stride
+            if (k && (q.D != a.p[net][k - 1].Dout || q.d_cs != a.p[net][k - 1].o_cs)) return false;
+        }
+    }
+    return true;
+}
+
+hipError_t launch_bwd_bf_layers(const BwdLayersArgs& a, hipStream_t s) {
+    if (!bwd_layers_ok(a)) return hipErrorInvalidValue;
+    const int blocks = a.C * (a.p[0][0].n_wg + a.p[1][0].n_wg);
+    hipLaunchKernelGGL(k_bwd_bf2_layers, dim3(blocks), dim3(BB_THREADS), BB_LDS, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_bwd_bf(const BwdArgs& a, hipStream_t s) {
     if (!bwd_bf_ok(a)) return hipErrorInvalidValue;

@@ -136,6 +136,18 @@ hipError_t launch_bwd(const BwdArgs& a, int nti, hipStream_t s);
 bool bwd_bf_ok(const BwdArgs& a);                       // k_bwd_bf handles every problem of the launch
 hipError_t launch_bwd_bf(const BwdArgs& a, hipStream_t s);
 
+// Layers nl - 1 .. 1 of both nets in one launch (k_bwd_bf2_layers): p[net][k] is the descriptor the per-layer launch
+// of layer nl - 1 - k would get, each net over its own nk = nl - 1 layers. 2 x 11 descriptors of 136 bytes: 3 KB of
+// the 4-KB kernel-argument segment.
+constexpr int BWD_LAYERS_MAXK = 11;
+struct BwdLayersArgs {
+    BwdProb p[2][BWD_LAYERS_MAXK];
+    int32_t nk[2], C;
+};
+static_assert(sizeof(BwdLayersArgs) <= 4096, "kernel-argument segment");
+bool bwd_layers_ok(const BwdLayersArgs& a);             // every layer a k_bwd_bf2 dX layer on its net's common chunks
+hipError_t launch_bwd_bf_layers(const BwdLayersArgs& a, hipStream_t s);
+
 // Whole-network backward in one launch for chunks of 64 rows (vihmc_bwd_chain.hip): every layer of both nets,
 // the deltas on chip, the same partial slabs as the per-layer k_bwd_bf2 launches. W_j^T from the pre-split W^T
 // image of layer j (BWD_WTIMG layout, index j - 1 of the net's images).

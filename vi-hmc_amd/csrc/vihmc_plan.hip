@@ -210,6 +210,7 @@ struct vihmc_plan {
     int fuse_scatter = 1;       // plan option: trajectory evaluations take theta already scattered by the leapfrog
     int mlp_fast = 1;             // plan option: the reference BNN shape on the register-resident kernels (vihmc_bnn.hip)
     int bwd_chain = 1;            // plan option: whole-network backward in one launch when the chunks are 64 rows
+    int bwd_layers = 1;           // plan option: layers nl - 1 .. 1 of a row chunk in one launch (k_bwd_bf2_layers)
     // Gram-form gradient-only contraction (vihmc_gram.hip) for the evaluations that return no log-prob (the
     // trajectory's inner leapfrog steps, vihmc_grad): plan options "gram" (on / off) and "gram_min_chains"
     // (gradient-only evaluation, Gram vs residual form, ms: C = 2 0.40 vs 0.34, C = 4 0.50 vs 0.53, C = 16 1.36 vs 1.48;
@@ -300,6 +301,8 @@ struct vihmc_plan {
     bool capturing = false;       // inside a hipGraph capture: no snapshot (the ring is host state)
     bool timg_live = false;       // the W^T images hold this evaluation's theta (scatter-kept or split this evaluation)
     bool last_bwd_chain = false;  // the last gradient evaluation ran k_bwd_chain (get_option bwd_chain: bit 1)
+    bool last_bwd_layers = false; // the last gradient evaluation ran k_bwd_bf2_layers (get_option bwd_layers: bit 1)
+    std::vector<char> bwd_tiled[2];   // per net and layer: its per-layer launch is a k_bwd_bf2 one (tiled slabs, jobsWt)
     float *g_theta = nullptr, *g_logp = nullptr, *g_grad = nullptr;
     int graph_on = -1;          // -1: follow VIHMC_GRAPH
     // hidden-layer forward products as exact 3-way bf16 splits (6 bf16 MFMA products, fp32 accumulate;
@@ -1045,7 +1048,7 @@ int build_deeponet(vihmc_plan* p, const vihmc_deeponet_desc* d, const float* xb,
         // two job lists over the same slabs: row-major (fp32 backward) and, for the layers the bf16x6 kernels run
         // (bwd_bf_ok per launch: layer i from the top of both nets), tiled
         std::vector<ReduceJob> jw, jt;
-        std::vector<char> tiled[2];
+        std::vector<char>(&tiled)[2] = p->bwd_tiled;
         for (int net = 0; net < 2; ++net) tiled[net].assign(p->nets[net].L.size(), 0);
         const int maxl = (int)std::max(p->nets[0].L.size(), p->nets[1].L.size());
         for (int i = 0; i < maxl; ++i) {
@@ -1565,54 +1568,81 @@ int deeponet_eval_body(vihmc_plan* p, const float* theta, int C, float* logp, fl
             HIPCHK(hipMemcpyAsync(p->dzb_snap, b.delta[0], sizeof(float) * b.delta_cs * C, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(p->dzt_snap, t.delta[0], sizeof(float) * t.delta_cs * C, hipMemcpyDeviceToDevice, s));
         }
-        // backward through both MLPs, last layer first: one fused launch per layer (branch + trunk
-        // grouped) computes delta_{l-1} and the dW / db partial slabs
+        // backward through both MLPs, last layer first: delta_{l-1} and the dW / db partial slabs of every layer, by
+        // k_bwd_chain (64-row chunks), else by one launch over layers nl - 1 .. 1 plus the input layers' launch, else
+        // by one launch per layer (branch + trunk grouped)
         int cur[2] = {0, 0};
         const int maxl = (int)std::max(b.L.size(), t.L.size());
-        // one event pair around the maxl consecutive layer launches (per-launch pairs cost ~4 % of the evaluation):
-        // the recorded time includes the maxl - 1 kernel boundaries between them
+        // one event pair around the whole backward (per-launch pairs cost ~4 % of the evaluation), counted as maxl
+        // layers whichever launches ran: the recorded time includes the kernel boundaries between them
         hipEvent_t bwd_stop = nullptr;
         if (int rc = p->timing_begin(VIHMC_T_BWD, s, &bwd_stop, maxl)) return rc;
         BwdChainArgs ca{};
         const bool chain = p->bwd_chain && p->bwd_bf16x6 && p->timg_live && bwd_chain_args(p, C, ca);
         if (chain) HIPCHK(launch_bwd_chain(ca, s));
         p->last_bwd_chain = chain;
+        // the per-layer launch's descriptor of layer j of a net: delta[cur] -> delta[cur ^ 1]
+        auto layer_prob = [&](int net, int j, int cur) {
+            Net& n = p->nets[net];
+            const LayerPk& L = n.L[j];
+            BwdProb q{};
+            q.D = n.delta[cur];
+            q.d_cs = n.delta_cs;
+            q.ldd = L.ldo;
+            q.WT = p->packed + L.wt;
+            q.wt_cs = p->dp;
+            q.ldw = L.ldo;
+            q.H = j == 0 ? n.input : n.act + n.h_off[j - 1];
+            q.h_cs = j == 0 ? 0 : n.act_cs;
+            q.ldh = L.ldi;
+            q.Dout = n.delta[cur ^ 1];
+            q.o_cs = n.delta_cs;
+            q.part = n.dwpart + L.part_off;
+            q.part_cs = n.dwpart_cs;
+            q.part_stride = (int32_t)L.part_stride;
+            q.M = n.rows;
+            q.n_out = L.n_out;
+            q.n_in = L.n_in;
+            q.act = j >= 1 ? n.L[j - 1].act : 0;
+            q.has_dx = j >= 1;
+            q.rows_per_wg = L.rows_per_chunk;
+            q.n_wg = L.n_chunks;
+            return q;
+        };
+        // layers nl - 1 .. 1 of both nets in one launch when each of them is a k_bwd_bf2 launch on its net's common
+        // chunks (bwd_tiled: the per-layer choice the tiled reduce jobs were built for); the input layers keep a
+        // launch of their own (no dX part, the branch one on shorter chunks)
+        bool layers = !chain && p->bwd_layers && p->bwd_bf16x6;
+        BwdLayersArgs la{};
+        la.C = C;
+        for (int net = 0; net < 2 && layers; ++net) {
+            const int nl = (int)p->nets[net].L.size();
+            layers = nl >= 2 && nl - 1 <= BWD_LAYERS_MAXK;
+            for (int j = nl - 1; j >= 1 && layers; --j) {
+                layers = p->bwd_tiled[net][j] != 0;
+                la.p[net][la.nk[net]] = layer_prob(net, j, la.nk[net] & 1);
+                ++la.nk[net];
+            }
+        }
+        layers = layers && bwd_layers_ok(la);
+        if (layers) HIPCHK(launch_bwd_bf_layers(la, s));
+        p->last_bwd_layers = layers;
         for (int i = 0; i < (chain ? 0 : maxl); ++i) {
             BwdArgs ba{};
             ba.C = C;
             int nti = 1;
+            bool bf = true;
             for (int net = 0; net < 2; ++net) {
                 Net& n = p->nets[net];
                 const int j = (int)n.L.size() - 1 - i;
-                if (j < 0) continue;
-                const LayerPk& L = n.L[j];
-                BwdProb& q = ba.p[ba.nprob++];
-                q.D = n.delta[cur[net]];
-                q.d_cs = n.delta_cs;
-                q.ldd = L.ldo;
-                q.WT = p->packed + L.wt;
-                q.wt_cs = p->dp;
-                q.ldw = L.ldo;
-                q.H = j == 0 ? n.input : n.act + n.h_off[j - 1];
-                q.h_cs = j == 0 ? 0 : n.act_cs;
-                q.ldh = L.ldi;
-                q.Dout = n.delta[cur[net] ^ 1];
-                q.o_cs = n.delta_cs;
-                q.part = n.dwpart + L.part_off;
-                q.part_cs = n.dwpart_cs;
-                q.part_stride = (int32_t)L.part_stride;
-                q.M = n.rows;
-                q.n_out = L.n_out;
-                q.n_in = L.n_in;
-                q.act = j >= 1 ? n.L[j - 1].act : 0;
-                q.has_dx = j >= 1;
-                q.rows_per_wg = L.rows_per_chunk;
-                q.n_wg = L.n_chunks;
-                nti = std::max(nti, nt_of(L.n_in));
+                if (j < 0 || (layers && j >= 1)) continue;
+                ba.p[ba.nprob++] = layer_prob(net, j, layers ? la.nk[net] & 1 : cur[net]);
+                bf = bf && p->bwd_tiled[net][j];
+                nti = std::max(nti, nt_of(n.L[j].n_in));
             }
             if (ba.nprob == 1) ba.p[1] = ba.p[0];
-            if (p->bwd_bf16x6 && bwd_bf_ok(ba)) HIPCHK(launch_bwd_bf(ba, s));
-            else HIPCHK(launch_bwd(ba, nti, s));
+            if (ba.nprob && p->bwd_bf16x6 && bf) HIPCHK(launch_bwd_bf(ba, s));
+            else if (ba.nprob) HIPCHK(launch_bwd(ba, nti, s));
             for (int net = 0; net < 2; ++net) {
                 const int j = (int)p->nets[net].L.size() - 1 - i;
                 if (j >= 1) cur[net] ^= 1;
@@ -2289,7 +2319,7 @@ int vihmc_timing_reset(vihmc_plan* p) {
     return 0;
 }
 
-#define OPTION_KEYS "fwd_bf16x6, contract_bf16x6, bwd_bf16x6, graph, timing_every, fwd_wimg, fwd_in0, skip_zt, fuse_scatter, img_scatter, mlp_fast, bwd_chain, gram, gram_active, gram_center, gram_pair2, tanh_cr, debug_dz, gram_min_chains, gram_guard, grad_evals, gram_evals, gram_chains, gram_chain_evals, y_masked, lik_count"
+#define OPTION_KEYS "fwd_bf16x6, contract_bf16x6, bwd_bf16x6, graph, timing_every, fwd_wimg, fwd_in0, skip_zt, fuse_scatter, img_scatter, mlp_fast, bwd_chain, bwd_layers, gram, gram_active, gram_center, gram_pair2, tanh_cr, debug_dz, gram_min_chains, gram_guard, grad_evals, gram_evals, gram_chains, gram_chain_evals, y_masked, lik_count"
 
 int vihmc_plan_option(vihmc_plan* p, const char* key, int value) {
     if (!p || !key) return fail("null argument");
@@ -2309,6 +2339,7 @@ int vihmc_plan_option(vihmc_plan* p, const char* key, int value) {
     else if (k == "img_scatter") p->img_by_scatter = value && p->smap_img;   // 0: split the images per evaluation
     else if (k == "mlp_fast") p->mlp_fast = value ? 1 : 0;
     else if (k == "bwd_chain") p->bwd_chain = value ? 1 : 0;
+    else if (k == "bwd_layers") p->bwd_layers = value ? 1 : 0;
     else if (k == "gram") p->gram = value ? 1 : 0;
     else if (k == "gram_min_chains") p->gram_min_chains = std::max(1, value);
     else if (k == "gram_guard") {                               // threshold 10^-value (0: off); history restarts
@@ -2367,6 +2398,7 @@ int vihmc_plan_get_option(const vihmc_plan* p, const char* key, int* value) {
     else if (k == "img_scatter") *value = p->img_by_scatter ? 1 : 0;
     else if (k == "mlp_fast") *value = p->mlp_fast && p->kind == 1 && mlp_bnn_fast_ok(p->mlp);
     else if (k == "bwd_chain") *value = p->bwd_chain | (p->last_bwd_chain ? 2 : 0);
+    else if (k == "bwd_layers") *value = p->bwd_layers | (p->last_bwd_layers ? 2 : 0);
     else if (k == "gram") *value = (p->gram && p->gram_alloc ? 1 : 0) | (p->last_gram ? 2 : 0);
     else if (k == "gram_min_chains") *value = p->gram_min_chains;
     // whether this plan's gradient-only evaluations can take the Gram form at all (gram, width, max_chains >=
